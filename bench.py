@@ -11,8 +11,15 @@ The 8 clients are spread over the N ranks (8/N clients per GPU, one process per 
 total work is fixed as N grows, so scaling is *strong*.  Data are synthetic ICU-shaped rows with a
 planted signal, weights are random-init (no datasets or checkpoints are downloadable here).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K rounds and prints one JSON line.  ``--dump-outputs DIR`` then writes
+what the last timed round computed as ``DIR/<name>.npy`` (see ``dump_outputs``); data, initial weights, client
+draws and batch orders are all seeded, so two runs with the same arguments train on identical inputs.
+``--full`` is where measurements beyond the headline figure belong; this benchmark has none that take a run of
+their own (baselines are the constants of BASELINE.md, per-phase timings are the opt-in ``--profile-rounds``),
+so today the flag changes nothing.
 """
 from __future__ import annotations
 
@@ -38,6 +45,41 @@ def shared_gpu_queues(ranks_per_gpu: int) -> int:
     return 4 if ranks_per_gpu <= 2 else (2 if ranks_per_gpu <= 8 else 1)
 
 
+DUMP_LIMIT_BYTES = 48 << 20  # per array; the arrays of one dump stay under 64 MB together
+
+
+def dump_outputs(path: str, eng, recs) -> None:
+    """What the last timed round handed to its caller, as ``<path>/<name>.npy``:
+
+    * ``global_params`` (float32 [P]): the aggregated global model after the round (``hyper_arena`` in hyper
+      mode: the hypernetwork's flat parameter arena),
+    * ``metric`` (float64 [1]): the round's server-side validation metric (ROC-AUC / accuracy),
+    * ``client_loss`` (float64 [clients, epochs]): every client's per-epoch training loss (NaN where a client
+      reports none: attackers and failed clients).
+
+    An array above ``DUMP_LIMIT_BYTES`` is replaced by a fixed, seeded sample of its elements."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    last = recs[-1]
+    arrays = {}
+    if eng.mode == "hyper" and getattr(eng, "hyper", None) is not None:
+        arrays["hyper_arena"] = eng.hyper.snapshot().detach().reshape(-1).to("cpu").numpy().astype(np.float32)
+    elif eng.global_params is not None:
+        arrays["global_params"] = eng.global_params.detach().reshape(-1).to("cpu").numpy().astype(np.float32)
+    arrays["metric"] = np.asarray([last["metric"]], np.float64)
+    losses = last.get("client_loss")
+    if losses:
+        width = max([len(l) for l in losses if l is not None] or [0])
+        arrays["client_loss"] = np.asarray([l if l is not None else [float("nan")] * width for l in losses],
+                                           np.float64).reshape(len(losses), width)
+    for name, a in arrays.items():
+        if a.nbytes > DUMP_LIMIT_BYTES:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, DUMP_LIMIT_BYTES // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -50,7 +92,13 @@ def main() -> int:
     ap.add_argument("--attackers", default="", help="idx:mode:round[:arg...] comma-separated (launch.py syntax)")
     ap.add_argument("--data-name", default="ICU")
     ap.add_argument("--profile-rounds", action="store_true", help="print per-phase timings to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed rounds, write the last round's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (none today: see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     if world_env > 1 and os.environ.get("AFL_BENCH_DEVICE") is not None:
         # several ranks on ONE GPU: cap each process's hardware queues so that all ranks' queues stay mapped
@@ -131,6 +179,8 @@ def main() -> int:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, recs)
     if os.environ.get("AFL_BENCH_TIMES") and rank == 0:  # per-round host timings of the timed rounds (JSONL)
         with open(os.environ["AFL_BENCH_TIMES"], "w") as f:
             for r in recs:
