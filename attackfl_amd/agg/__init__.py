@@ -15,6 +15,7 @@ Each rule returns ``AggResult(params [P] | None, ok, info)``.  Rows are in clien
   norm clip + cosine filter + FedAvg of the kept originals
 * fltracer      ``src/Utils.py:359-369`` (dormant in the reference)  PCA(1) + MAD z-score
 * byzantine     ``src/Utils.py:218-248`` (dead code in the reference) cosine ≥ 0.9 to model 0
+Beyond the reference (docs/PARITY.md): multi_krum, bulyan (assumed Byzantine count ``byz-f``) and geomed (RFA).
 FLTrust and the hypernetwork live in ``fl/server.py`` (they need training).
 """
 from __future__ import annotations
@@ -103,6 +104,56 @@ def krum(U: torch.Tensor, sizes=None, f_rate: float = 0.0, **_) -> AggResult:
     scores = torch.sort(d2, dim=1).values[:, :m].sum(dim=1)
     sel = torch.argmin(scores)
     return AggResult(U.index_select(0, sel.reshape(1))[0], True, {"selected": sel, "f": f, "scores": scores})
+
+
+def byzantine_count(n: int, byz_f="auto", per_f: int = 4, rule: str = "bulyan") -> int:
+    """The assumed number f of Byzantine rows (engine ``byz-f``).  ``auto``: max(0, (n - 3) // 4), the largest f
+    Bulyan admits.  An explicit f >= 1 must leave n >= per_f * f + 3 rows (2 f + 3 for Multi-Krum, 4 f + 3 for
+    Bulyan); f = 0 claims no tolerance and is admitted for any n."""
+    if byz_f is None or byz_f == "auto":
+        return max(0, (n - 3) // 4)
+    f = int(byz_f)
+    if f < 0:
+        raise ValueError(f"byz-f must be 'auto' or an integer >= 0 (got {byz_f}).")
+    if f > 0 and n < per_f * f + 3:
+        raise ValueError(f"Too few clients for {rule} with byz-f = {f}: n = {n}, needs n >= {per_f} f + 3 = "
+                         f"{per_f * f + 3}.")
+    return f
+
+
+def multi_krum(U: torch.Tensor, sizes=None, byz_f="auto", **_) -> AggResult:
+    """Multi-Krum (Blanchard et al., NeurIPS 2017; beyond the reference, whose ``krum`` keeps f = 0, A-11): Krum scores
+    with k = max(n - f - 2, 1) neighbours on all rows, the n - f rows with the smallest (score, index), their
+    size-weighted mean.  One ``k_krum_select`` launch on the Gram-form distances; no host read."""
+    n = U.shape[0]
+    f = byzantine_count(n, byz_f, 2, "multi_krum")
+    _, keep, scores = ops.krum_select(ops.pairwise_sqdist(U), f, n - f, False)
+    w = torch.ones(n, dtype=torch.float64) if sizes is None else sizes
+    w = _device_weights(w, U.device) * keep.double()
+    return AggResult(ops.weighted_rows(U, w / w.sum()), True, {"selected": keep, "f": f, "scores": scores})
+
+
+def bulyan(U: torch.Tensor, sizes=None, byz_f="auto", **_) -> AggResult:
+    """Bulyan (El Mhamdi et al., ICML 2018; beyond the reference): theta = n - 2 f rows by iterated Krum (re-scored on
+    the rows still active before every pick), then per column the unweighted mean of the beta = theta - 2 f values
+    closest to the lower median of the selected ones.  Two launches after the distances (``k_krum_select``,
+    ``k_bulyan_coord`` on the device index list); no host read: theta, beta and the kernel variant follow from n, f."""
+    n = U.shape[0]
+    f = byzantine_count(n, byz_f, 4, "bulyan")
+    theta = n - 2 * f
+    sel, keep, scores = ops.krum_select(ops.pairwise_sqdist(U), f, theta, True)
+    return AggResult(ops.bulyan_coord(U, sel, theta - 2 * f), True, {"selected": keep, "f": f, "scores": scores})
+
+
+def geomed(U: torch.Tensor, sizes=None, geomed_iters: int = 100, geomed_nu: float = 1e-6, **_) -> AggResult:
+    """Geometric median by the smoothed Weiszfeld iteration of RFA (Pillutla et al., 2022; beyond the reference),
+    weighted by alpha = sizes / sum sizes, run in Gram space on the n x n centred Gram (``k_geomed_weights``): the
+    rows are read by the Gram pass and by the final ``weighted_rows`` only.  No host read."""
+    n = U.shape[0]
+    a = torch.ones(n, dtype=torch.float64) if sizes is None else sizes
+    a = _device_weights(a, U.device)
+    w, iters, obj = ops.geomed_weights(_centred_gram(U), a / a.sum(), int(geomed_iters), float(geomed_nu))
+    return AggResult(ops.weighted_rows(U, w), True, {"weights": w, "iters": iters, "objective": obj})
 
 
 def shieldfl(U: torch.Tensor, sizes=None, **_) -> AggResult:
@@ -399,6 +450,9 @@ AGGREGATORS = {
     "trimmed_mean": trimmed_mean,
     "median": median,
     "krum": krum,
+    "multi_krum": multi_krum,
+    "bulyan": bulyan,
+    "geomed": geomed,
     "shieldfl": shieldfl,
     "gmm": gmm,
     "scionfl": scionfl,

@@ -20,6 +20,10 @@ Extensions (all optional, defaults keep reference behaviour):
 ``data:``
   synthetic: auto | true | false   (auto = use the reference pickles when present)
   train-size / test-size / seed / har-train-size / har-test-size
+``server:``
+  mode: the reference's modes plus multi_krum | bulyan | geomed (Multi-Krum, Bulyan and the geometric median /
+        RFA: defences that assume f >= 1 Byzantine clients; ``krum`` keeps the reference's f = 0, A-11; definitions
+        in docs/PARITY.md)
 ``engine:``
   trainer: auto | fused | graph | eager | oracle  (fused = HIP persistent TransformerModel / RNNModel
                                     kernels; graph = HIP-graph-replayed layer programs for CNN/RNN/HAR models;
@@ -43,6 +47,12 @@ Extensions (all optional, defaults keep reference behaviour):
   fault-inject: [{client, round}]   (NaN-poison a client's model before that training round)
   gmm-rank: int                     (gmm mode's PCA rank, default 1; 0 = max(1, min(4, n // 2 - 1)), the
                                     round-5 rule: profiles/gmm_rank_study_r6.md)
+  byz-f: auto | int >= 0            (multi_krum / bulyan: the assumed number f of Byzantine clients; auto =
+                                    max(0, (n - 3) // 4), the largest f Bulyan admits; an explicit f >= 1 needs
+                                    n >= 2 f + 3 (multi_krum) or n >= 4 f + 3 (bulyan) or the round raises)
+  geomed-iters: int >= 1            (geomed: at most that many smoothed-Weiszfeld iterations, default 100; fewer
+                                    once the objective moves by <= 1e-9 of itself)
+  geomed-nu: float > 0              (geomed: the smoothing floor of the distances, default 1e-6, the RFA value)
   save-state: bool                  (write {model}.state.pt + {model}.clients.r{rank}.pt every round)
   resume: bool                      (continue from those files: counters, RNGs, optimizer moments)
 """
@@ -56,7 +66,7 @@ from typing import Any, Dict, List, Optional
 import yaml
 
 SERVER_MODES = ("fedavg", "hyper", "FLTrust", "trimmed_mean", "shieldfl", "gmm", "krum", "median", "scionfl",
-                "fltracer", "byzantine")
+                "fltracer", "byzantine", "multi_krum", "bulyan", "geomed")
 ATTACK_MODES = ("Random", "Min-Max", "Min-Sum", "Opt-Fang", "LIE")
 MODEL_NAMES = ("CNNModel", "RNNModel", "TransformerModel", "TransformerClassifier")
 DATA_NAMES = ("ICU", "HAR", "CIFAR10")
@@ -91,7 +101,8 @@ EXTENSION_DEFAULTS: Dict[str, Any] = {
     "engine": {"trainer": "auto", "distance": "spectral", "seed": 0, "metrics": "", "checkpoint-dir": ".",
                "async-checkpoint": True, "compat-hyper-resume": False, "compat-fltrust": False, "max-retries": 50, "trace": False,
                "phase-sync": False, "fault-inject": [], "save-state": False, "resume": False,
-               "speculative": True, "compat-har-train": False, "compat-fedavg-alias": False, "gmm-rank": 1},
+               "speculative": True, "compat-har-train": False, "compat-fedavg-alias": False, "gmm-rank": 1,
+               "byz-f": "auto", "geomed-iters": 100, "geomed-nu": 1e-6},
 }
 
 
@@ -246,6 +257,18 @@ class Config:
             raise ValueError("server.clients must be >= 1")
         if self.engine["distance"] not in ("spectral", "flat"):
             raise ValueError("engine.distance must be 'spectral' or 'flat'")
+        f = self.engine.get("byz-f", "auto")
+        if f != "auto" and (isinstance(f, bool) or not isinstance(f, int) or f < 0):
+            raise ValueError(f"engine.byz-f must be 'auto' or an integer >= 0 (got {f!r})")
+        it, nu = self.engine.get("geomed-iters", 100), self.engine.get("geomed-nu", 1e-6)
+        if isinstance(it, bool) or not isinstance(it, int) or it < 1:
+            raise ValueError(f"engine.geomed-iters must be an integer >= 1 (got {it!r})")
+        try:  # (YAML 1.1 reads "1e-6", without a dot, as a string)
+            nu_ok = not isinstance(nu, bool) and float(nu) > 0
+        except (TypeError, ValueError):
+            nu_ok = False
+        if not nu_ok:
+            raise ValueError(f"engine.geomed-nu must be a number > 0 (got {nu!r})")
         return self
 
     def to_dict(self) -> Dict[str, Any]:

@@ -54,7 +54,8 @@ from .trainers import Plan, make_plan, make_trainer
 # are enqueued before the host waits for the training, as for FedAvg (FLEngine._early_launch).  gmm (whose
 # success the host reads after its wait, from a copy queued before the next launch) and FLTrust (server-model
 # training + trust weights, device work too) take the early launch through branches of their own
-EARLY_AGGREGATORS = ("trimmed_mean", "median", "krum", "shieldfl", "scionfl", "fltracer", "byzantine")
+EARLY_AGGREGATORS = ("trimmed_mean", "median", "krum", "shieldfl", "scionfl", "fltracer", "byzantine", "multi_krum",
+                     "bulyan", "geomed")
 
 META = 5  # valid, result, size, is_attacker, decision word; then the client's per-epoch losses (E columns)
 DECISION = 4  # column of the sender's decision word (``FLEngine._decision_word``)
@@ -782,6 +783,12 @@ class FLEngine:
     # ------------------------------------------------------------------------------------------
     # SERVER
     # ------------------------------------------------------------------------------------------
+    def _rule_args(self) -> dict:
+        """The engine keys of multi_krum / bulyan (``byz-f``) and geomed (``geomed-iters``, ``geomed-nu``)."""
+        e = self.cfg.engine
+        return {"byz_f": e.get("byz-f", "auto"), "geomed_iters": int(e.get("geomed-iters", 100)),
+                "geomed_nu": float(e.get("geomed-nu", 1e-6))}
+
     def _aggregate(self, U: torch.Tensor, sizes: torch.Tensor, attackers: torch.Tensor, round_ok: bool) -> dict:
         info: dict = {}
         if not round_ok:
@@ -803,7 +810,7 @@ class FLEngine:
             return info
         fn = AGGREGATORS[mode]
         res: AggResult = fn(U, sizes, attackers=attackers, seed=self.seed * 13 + self.round_no,
-                            gmm_rank=int(self.cfg.engine.get("gmm-rank", 1)))
+                            gmm_rank=int(self.cfg.engine.get("gmm-rank", 1)), **self._rule_args())
         info.update({k: v for k, v in res.info.items() if k != "scores"})
         if not res.ok:
             info["agg_failed"] = True
@@ -1145,7 +1152,7 @@ class FLEngine:
         elif self.mode != "fedavg":
             # a robust rule, all on the device (no host read): its result kept only when every client succeeded
             res = AGGREGATORS[self.mode](U, sizes, attackers=None, seed=self.seed * 13 + self.round_no,
-                                        gmm_rank=int(self.cfg.engine.get("gmm-rank", 1)))
+                                        gmm_rank=int(self.cfg.engine.get("gmm-rank", 1)), **self._rule_args())
             g = torch.where(ok_all, res.params.to(torch.float32), g_old)  # (a new tensor: never a row of U)
             self._early_agg_info = {k: v for k, v in res.info.items() if k != "scores"}
         else:

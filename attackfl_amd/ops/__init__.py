@@ -302,6 +302,34 @@ def trimmed_mean(U: torch.Tensor, trim_k: int) -> torch.Tensor:
     return composite.trimmed_mean(U, trim_k)
 
 
+def krum_select(D: torch.Tensor, f: int, rounds: int, iterated: bool):
+    """Krum selection on the squared-distance matrix -> (sel [rounds] in selection order, mask [n] bool, first-pass
+    scores [n] fp64).  Device, n <= 64: ``k_krum_select`` (one launch, no host read); the composite beyond."""
+    if _dev(D) and D.shape[0] <= 64:
+        sel, mask, scores = native().krum_select(D.to(torch.float64).contiguous(), int(f), int(rounds), bool(iterated))
+        return sel, mask.bool(), scores
+    return composite.krum_select(D, int(f), int(rounds), bool(iterated))
+
+
+def bulyan_coord(U: torch.Tensor, sel: torch.Tensor, beta: int) -> torch.Tensor:
+    """Per column, the mean of the ``beta`` values closest to the lower median over the rows ``sel`` of U (a device
+    index list on the device path: ``k_bulyan_coord`` reads the selected rows in place)."""
+    if _dev(U) and sel.numel() <= 64:
+        return native().bulyan_coord(U.contiguous(), sel.to(device=U.device, dtype=torch.int32).contiguous(), int(beta))
+    return composite.bulyan_coord(U, sel, int(beta))
+
+
+def geomed_weights(G: torch.Tensor, alpha: torch.Tensor, iters: int = 100, nu: float = 1e-6):
+    """Smoothed-Weiszfeld weights from the centred Gram matrix -> (weights [n] fp64, iterations, objective), the
+    last two 0-d tensors.  Device, n <= 64: ``k_geomed_weights``."""
+    if _dev(G) and G.shape[0] <= 64:
+        w, info = native().geomed_weights(G.to(torch.float64).contiguous(),
+                                          alpha.to(device=G.device, dtype=torch.float64).contiguous(), int(iters),
+                                          float(nu))
+        return w, info[0].to(torch.int32), info[1]
+    return composite.geomed_weights(G, alpha.to(G.device), int(iters), float(nu))
+
+
 def row_norms(U: torch.Tensor) -> torch.Tensor:
     if _dev(U):
         return native().row_dots(U.contiguous(), U.new_zeros(0), 0)[:, 0].clamp_min(0).sqrt()

@@ -120,6 +120,76 @@ def trimmed_mean(U: torch.Tensor, trim_k: int) -> torch.Tensor:
     return s[trim_k:n - trim_k].mean(dim=0)
 
 
+def krum_select(D: torch.Tensor, f: int, rounds: int, iterated: bool):
+    """Krum's selection on the squared-distance matrix ``D [n, n]`` (``agg.hip`` ``k_krum_select``): score(i) on an
+    active set of m rows = the k = max(m - f - 2, 1) smallest D[i][j] over the active j != i, summed in ascending
+    order (0 for m = 1); a pick is the active row with the smallest (score, index).  ``iterated`` False: scored once,
+    ``rounds`` picks by that ranking (Multi-Krum); True: re-scored on the rows still active before every pick
+    (Bulyan).  -> (sel [rounds] int64 in selection order, mask [n] bool, first-pass scores [n] fp64).  Tensor ops
+    only (no host read), so it also serves device tensors beyond the kernel's 64 rows."""
+    n = D.shape[0]
+    # D is read as symmetric, the upper triangle standing for both halves: at k = 1 (Bulyan's last picks) two rows that
+    # are each other's nearest neighbour tie exactly, which a D[i][j] != D[j][i] in the last bit would decide
+    D = torch.triu(D.double(), 1)
+    D = D + D.t()
+    inf = float("inf")
+    idx = torch.arange(n, device=D.device)
+    eye = idx[:, None] == idx[None, :]
+    active = torch.ones(n, dtype=torch.bool, device=D.device)
+    sel, first, sc = [], None, None
+    for t in range(rounds):
+        if t == 0 or iterated:
+            m = n - t if iterated else n
+            k = max(m - f - 2, 1)
+            if m == 1:
+                sc = torch.zeros(n, dtype=torch.float64, device=D.device)
+            else:
+                W = D.masked_fill(eye | ~active[None, :], inf)
+                sc = torch.cumsum(torch.sort(W, dim=1).values, dim=1)[:, k - 1]
+            if t == 0:
+                first = sc
+        i = torch.argmin(torch.where(active, sc, torch.full_like(sc, inf)))  # (ties: the first, lowest index)
+        sel.append(i)
+        active = active & (idx != i)
+    return torch.stack(sel), ~active, first
+
+
+def bulyan_coord(U: torch.Tensor, sel: torch.Tensor, beta: int) -> torch.Tensor:
+    """Bulyan's coordinate step over the rows ``sel`` of U: per column the mean of the ``beta`` values with the
+    smallest key (|x - med| in fp32, x), med the lower median (``k_bulyan_coord``)."""
+    S = torch.sort(U.index_select(0, sel.long()), dim=0).values
+    med = S[(S.shape[0] - 1) // 2]
+    # S ascends, so a stable sort of the distances breaks their ties towards the smaller value
+    order = torch.sort((S - med[None, :]).abs(), dim=0, stable=True).indices[:beta]
+    return (S.gather(0, order).double().sum(dim=0) / beta).to(U.dtype)
+
+
+def geomed_weights(G: torch.Tensor, alpha: torch.Tensor, iters: int, nu: float):
+    """Smoothed Weiszfeld in Gram space (``k_geomed_weights``): G the centred Gram [n, n], alpha on the simplex ->
+    (weights [n] fp64, iterations, objective).  The stop test is kept on the tensor's device (a CPU run also
+    leaves the loop at it)."""
+    G, a = G.double(), alpha.double()
+    diag = G.diagonal()
+    b = a.clone()
+    obj = torch.zeros((), dtype=torch.float64, device=G.device)
+    prev = torch.full_like(obj, float("inf"))
+    it = torch.zeros((), dtype=torch.int32, device=G.device)
+    done = torch.zeros((), dtype=torch.bool, device=G.device)
+    for _ in range(int(iters)):
+        gb = G @ b
+        d = (diag - 2.0 * gb + b @ gb).clamp_min(0.0).sqrt()
+        o = (a * d).sum()
+        nb = a / d.clamp_min(nu)
+        b = torch.where(done, b, nb / nb.sum())
+        obj = torch.where(done, obj, o)
+        it = it + (~done).to(torch.int32)
+        done = done | ((o - prev).abs() <= 1e-9 * o)
+        prev = o
+        if not G.is_cuda and bool(done):
+            break
+    return b, it, obj
+
+
 def row_norms(U: torch.Tensor) -> torch.Tensor:
     return torch.linalg.vector_norm(U.double(), dim=1)
 

@@ -118,6 +118,60 @@ torch::Tensor top_pc(torch::Tensor G, int64_t sweeps) {
   return z;
 }
 
+// Krum selection (agg.multi_krum / agg.bulyan): D [n, n] fp64 -> (sel [rounds] int32 in selection order, mask [n]
+// uint8, first-pass scores [n] fp64)
+std::vector<torch::Tensor> krum_select(torch::Tensor D, int64_t f, int64_t rounds, bool iterated) {
+  check_dev(D, "D", torch::kFloat64);
+  const int64_t n = D.size(0);
+  TORCH_CHECK(D.dim() == 2 && D.size(1) == n && n >= 1 && n <= 64, "krum_select: D [n, n], n <= 64");
+  TORCH_CHECK(f >= 0 && f <= n && rounds >= 1 && rounds <= n, "krum_select: n = ", n, " needs 0 <= f <= n and 1 <= ",
+              "rounds <= n (got f = ", f, ", rounds = ", rounds, ")");
+  auto sel = torch::zeros({rounds}, D.options().dtype(torch::kInt32));
+  auto mask = torch::zeros({n}, D.options().dtype(torch::kUInt8));
+  auto scores = torch::zeros({n}, D.options());
+  TORCH_CHECK(afl_krum_select(D.data_ptr<double>(), (int)n, (int)f, (int)rounds, iterated ? 1 : 0, sel.data_ptr<int>(),
+                              mask.data_ptr<uint8_t>(), scores.data_ptr<double>(), cur()) == 0,
+              "krum_select launch failed");
+  AFL_CHECK_LAUNCH();
+  return {sel, mask, scores};
+}
+
+// Bulyan's coordinate step (agg.bulyan): U [N, P] fp32, sel [theta] int32 (device) -> [P]
+torch::Tensor bulyan_coord(torch::Tensor U, torch::Tensor sel, int64_t beta) {
+  check_dev(U, "U", torch::kFloat32);
+  check_dev(sel, "sel", torch::kInt32);
+  TORCH_CHECK(U.dim() == 2 && U.size(0) >= 1 && U.size(1) >= 1, "bulyan_coord: U [N, P]");
+  const int64_t N = U.size(0), theta = sel.numel();
+  const long P = U.size(1);
+  TORCH_CHECK(N <= INT_MAX && theta >= 1 && theta <= 64 && theta <= N && beta >= 1 && beta <= theta,
+              "bulyan_coord: needs 1 <= beta <= theta <= min(N, 64) (got N = ", N, ", theta = ", theta, ", beta = ", beta,
+              ")");
+  auto out = torch::empty({P}, U.options());
+  TORCH_CHECK(afl_bulyan_coord(U.data_ptr<float>(), (int)N, P, sel.data_ptr<int>(), (int)theta, (int)beta,
+                               out.data_ptr<float>(), cur()) == 0, "bulyan_coord launch failed");
+  AFL_CHECK_LAUNCH();
+  return out;
+}
+
+// smoothed Weiszfeld weights (agg.geomed): G centred Gram [n, n] fp64, alpha [n] fp64 -> (w [n] fp64, info [2] fp64
+// {iterations, objective})
+std::vector<torch::Tensor> geomed_weights(torch::Tensor G, torch::Tensor alpha, int64_t iters, double nu) {
+  check_dev(G, "G", torch::kFloat64);
+  check_dev(alpha, "alpha", torch::kFloat64);
+  const int64_t n = G.size(0);
+  TORCH_CHECK(G.dim() == 2 && G.size(1) == n && alpha.numel() == n && n >= 1 && n <= 64,
+              "geomed_weights: G [n, n], alpha [n], n <= 64");
+  TORCH_CHECK(iters >= 1 && iters <= INT_MAX && nu > 0.0, "geomed_weights: iters >= 1 and nu > 0 (got ", iters, ", ", nu,
+              ")");
+  auto w = torch::zeros({n}, G.options());
+  auto info = torch::zeros({2}, G.options());
+  TORCH_CHECK(afl_geomed_weights(G.data_ptr<double>(), alpha.data_ptr<double>(), (int)n, (int)iters, nu,
+                                 w.data_ptr<double>(), info.data_ptr<double>(), cur()) == 0,
+              "geomed_weights launch failed");
+  AFL_CHECK_LAUNCH();
+  return {w, info};
+}
+
 // Gram matrix of the rows centred on the MEAN row (PCA of the updates: agg.fltracer / agg.gmm), through the same
 // fp64-MFMA pass (rows centred on row 0, H) followed by the double centring C = H - rowmean - colmean + mean
 std::vector<torch::Tensor> gram_centred(torch::Tensor G) {
@@ -800,6 +854,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("row_dots", &row_dots);
   m.def("gmm_filter", &gmm_filter, pybind11::arg("G"), pybind11::arg("att"), pybind11::arg("rank") = 0);
   m.def("top_pc", &top_pc);
+  m.def("krum_select", &krum_select);
+  m.def("bulyan_coord", &bulyan_coord);
+  m.def("geomed_weights", &geomed_weights);
   m.def("fxsum_test", &fxsum_test);
   m.def("gram_centred", &gram_centred);
   m.def("stoch_quant", &stoch_quant);

@@ -432,6 +432,18 @@ int afl_gmm_filter(const double* G, int n, const unsigned char* att, unsigned ch
                    hipStream_t s);
 // FLTracer PCA(1) scores from the centred Gram [n][n] fp64 (n <= 64): Jacobi eigen-decomposition, z [n] fp64
 int afl_top_pc(const double* G, int n, int sweeps, double* z, hipStream_t s);
+// Krum selection on the squared-distance matrix D [n][n] fp64 (n <= 64; agg.hip k_krum_select): ``rounds`` rows by
+// (score, index), scored once (iterated = 0, Multi-Krum) or on the rows still active before every pick (iterated = 1,
+// Bulyan) -> sel [rounds] int32 in selection order, mask [n] 0/1, scores [n] fp64 of the first pass
+int afl_krum_select(const double* D, int n, int f, int rounds, int iterated, int* sel, unsigned char* mask,
+                    double* scores, hipStream_t s);
+// Bulyan's coordinate step over the theta rows sel[] of U [N][P] (agg.hip k_bulyan_coord): per column the mean of the
+// beta values closest to the lower median
+int afl_bulyan_coord(const float* U, int N, long P, const int* sel, int theta, int beta, float* out, hipStream_t s);
+// smoothed Weiszfeld in Gram space (agg.hip k_geomed_weights): G centred Gram [n][n] fp64, alpha [n] fp64 on the
+// simplex -> w [n] fp64, info = {iterations, objective}
+int afl_geomed_weights(const double* G, const double* alpha, int n, int iters, double nu, double* w, double* info,
+                       hipStream_t s);
 void afl_noise_philox(const float* own, float* out, long P, float sigma, uint64_t seed, hipStream_t s);
 
 // comm.hip — one-shot intra-node all-gather over IPC-mapped peer buffers (xGMI)

@@ -10,6 +10,9 @@
 //   row_dots        <u,u>, <u,r>, <r,r> per row                                      K-G8
 //   stoch_quant     ScionFL 1-bit stochastic quantisation                            K-G9
 //   adam_flat       Adam over a flat arena (optional grad scale = clip coefficient)  K-O1
+//   krum_select     Multi-Krum ranking / Bulyan iterated selection on the distance matrix (beyond the reference)
+//   bulyan_coord    Bulyan's mean of the beta values closest to the column median, over selected rows
+//   geomed_weights  smoothed Weiszfeld (geometric median, RFA) in Gram space
 //
 // Every reduction is two-pass with a fixed summation order (no float atomics), so results are
 // bit-identical across ranks: the replicated server state on each rank stays in lock-step.
@@ -889,5 +892,216 @@ __global__ void __launch_bounds__(64) k_top_pc(const double* __restrict__ G, int
 int afl_top_pc(const double* G, int n, int sweeps, double* z, hipStream_t s) {
   if (n < 1 || n > GMM_MAXN || sweeps < 1) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_top_pc, dim3(1), dim3(64), 0, s, G, n, sweeps, z);
+  return (int)hipGetLastError();
+}
+
+// ============================================================================ krum_select
+// Krum's selection on the squared-distance matrix D [n][n] (fp64, n <= 64), the shared step of Multi-Krum (Blanchard
+// et al.) and Bulyan (El Mhamdi et al.).  score(i) on an active set of m rows = the sum, in ascending order of value,
+// of the k = max(m - f - 2, 1) smallest D[i][j] over the active j != i (0 when m = 1); a pick is the active row with the
+// smallest (score, index).  iterated = 0: the rows are scored once on the full set and ``rounds`` picks follow that
+// ranking; iterated = 1: every pick re-scores the rows still active and deactivates the winner.
+// One wave, lane i owns row i: it sorts its row once (stable insertion sort of (value, column) in LDS, row stride
+// n_max + 1 words so that the lanes' rows fall into different banks), after which a score is one walk along the sorted
+// row that skips the inactive columns.  The active set is a 64-bit mask every lane holds; the pick is a butterfly
+// reduction on (score, index) whose result is taken from lane 0, so the mask stays wave-uniform whatever the scores
+// hold (a NaN compares as a tie and falls to the lower index; an active row always wins over an inactive one, so
+// sel[] only ever holds indices in [0, n)).
+// D is read as a symmetric matrix, its upper triangle standing for both halves: with k = 1 (Bulyan's last picks) two
+// rows that are each other's nearest neighbour tie EXACTLY, and the tie rule only means something if D[i][j] and
+// D[j][i] are the same bits (a Gram product computed as a full matrix product may differ in the last bit).
+constexpr int KS_LD = GMM_MAXN + 1;
+
+__global__ void __launch_bounds__(64) k_krum_select(const double* __restrict__ D, int n, int f, int rounds, int iterated,
+                                                    int* __restrict__ sel, unsigned char* __restrict__ mask,
+                                                    double* __restrict__ scores) {
+  __shared__ double V[GMM_MAXN * KS_LD];
+  __shared__ unsigned char J[GMM_MAXN * KS_LD];
+  const int i = threadIdx.x;
+  for (int e = i; e < n * n; e += 64) {
+    const int r = e / n, c = e - r * n;
+    V[r * KS_LD + c] = r <= c ? D[e] : D[c * n + r];  // (the upper triangle, see above)
+    J[r * KS_LD + c] = (unsigned char)c;
+  }
+  __syncthreads();
+  if (i < n) {
+    double* v = V + i * KS_LD;
+    unsigned char* jx = J + i * KS_LD;
+    for (int p = 1; p < n; ++p) {
+      const double x = v[p];
+      const unsigned char jp = jx[p];
+      int q = p - 1;
+      while (q >= 0 && v[q] > x) {
+        v[q + 1] = v[q];
+        jx[q + 1] = jx[q];
+        --q;
+      }
+      v[q + 1] = x;
+      jx[q + 1] = jp;
+    }
+  }
+  unsigned long long act = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
+  double sc = 0.0;
+  for (int t = 0; t < rounds; ++t) {
+    const bool mine = i < n && ((act >> i) & 1ull);
+    if (t == 0 || iterated) {
+      const int m = iterated ? n - t : n;
+      const int k = max(m - f - 2, 1);
+      sc = 0.0;
+      if (mine) {
+        int cnt = 0;
+        for (int p = 0; p < n && cnt < k; ++p) {
+          const int j = J[i * KS_LD + p];
+          if (j != i && ((act >> j) & 1ull)) {
+            sc += V[i * KS_LD + p];
+            ++cnt;
+          }
+        }
+      }
+      if (t == 0 && i < n) scores[i] = sc;
+    }
+    int bi = mine ? i : 64;
+    double bs = sc;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double os = __shfl_xor(bs, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      const bool take = oi < 64 && (bi >= 64 || os < bs || (!(bs < os) && oi < bi));
+      bs = take ? os : bs;
+      bi = take ? oi : bi;
+    }
+    bi = __shfl(bi, 0, 64) & 63;  // (rounds <= n: an active row exists, so the index is one of [0, n))
+    if (i == 0) sel[t] = bi;
+    act &= ~(1ull << bi);
+  }
+  if (i < n) mask[i] = ((act >> i) & 1ull) ? 0 : 1;
+}
+
+int afl_krum_select(const double* D, int n, int f, int rounds, int iterated, int* sel, unsigned char* mask,
+                    double* scores, hipStream_t s) {
+  if (n < 1 || n > GMM_MAXN || f < 0 || f > n || rounds < 1 || rounds > n || (iterated != 0 && iterated != 1))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_krum_select, dim3(1), dim3(64), 0, s, D, n, f, rounds, iterated, sel, mask, scores);
+  return (int)hipGetLastError();
+}
+
+// ============================================================================ bulyan_coord
+// Bulyan's coordinate step: per column, over the theta rows sel[0 .. theta) of U (a device index list: no gathered
+// copy of the rows), the mean of the beta values closest to the lower median (sorted position (theta - 1) / 2, as
+// coord_select's median).  One thread per column, the k_coord_select register sort (NaN last), then a two-pointer
+// expansion from the median position: the beta smallest keys (|x - med| in fp32, x) are contiguous in sorted order, and
+// on an equal distance the left neighbour, the smaller value, is taken.  Registers are only indexed by compile-time
+// constants (the neighbours come out of predicated sweeps), the window is summed in fp64 in sorted order.
+// A row index is clamped into [0, N) before it is used as an address.
+template <int NMAX>
+__global__ void __launch_bounds__(256) k_bulyan_coord(const float* __restrict__ U, int N, long P,
+                                                      const int* __restrict__ sel, int theta, int beta,
+                                                      float* __restrict__ out) {
+  long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= P) return;
+  float v[NMAX];
+#pragma unroll
+  for (int i = 0; i < NMAX; ++i) {
+    float x = __int_as_float(0x7f800000);
+    if (i < theta) {
+      const int r = min(max(sel[i], 0), N - 1);
+      x = U[(long)r * P + c];
+    }
+    v[i] = x;
+  }
+#pragma unroll
+  for (int r = 0; r < NMAX; ++r) {
+#pragma unroll
+    for (int i = (r & 1); i + 1 < NMAX; i += 2) {
+      float a = v[i], b = v[i + 1];
+      bool sw = (a > b) || (a != a && b == b);
+      v[i] = sw ? b : a;
+      v[i + 1] = sw ? a : b;
+    }
+  }
+  const int mid = (theta - 1) / 2;
+  float med = 0.f;
+#pragma unroll
+  for (int i = 0; i < NMAX; ++i) med = (i == mid) ? v[i] : med;
+  int lo = mid, hi = mid;
+  for (int s = 1; s < beta; ++s) {
+    float a = 0.f, b = 0.f;  // the neighbours v[lo - 1], v[hi + 1]
+#pragma unroll
+    for (int i = 0; i < NMAX; ++i) {
+      a = (i == lo - 1) ? v[i] : a;
+      b = (i == hi + 1) ? v[i] : b;
+    }
+    const bool left = lo > 0 && (hi + 1 >= theta || fabsf(a - med) <= fabsf(b - med));
+    // (beta <= theta: one side is inside the list while the window is short; a NaN distance goes right first)
+    if (left || hi + 1 >= theta) lo = max(lo - 1, 0);
+    else ++hi;
+  }
+  double acc = 0.0;
+#pragma unroll
+  for (int i = 0; i < NMAX; ++i) acc += (i >= lo && i <= hi) ? (double)v[i] : 0.0;
+  out[c] = (float)(acc / (double)beta);
+}
+
+int afl_bulyan_coord(const float* U, int N, long P, const int* sel, int theta, int beta, float* out, hipStream_t s) {
+  if (N < 1 || P < 1 || theta < 1 || theta > N || theta > 64 || beta < 1 || beta > theta)
+    return (int)hipErrorInvalidValue;
+  dim3 g(afl_cdiv(P, 256)), b(256);
+  if (theta <= 8) hipLaunchKernelGGL(k_bulyan_coord<8>, g, b, 0, s, U, N, P, sel, theta, beta, out);
+  else if (theta <= 16) hipLaunchKernelGGL(k_bulyan_coord<16>, g, b, 0, s, U, N, P, sel, theta, beta, out);
+  else if (theta <= 32) hipLaunchKernelGGL(k_bulyan_coord<32>, g, b, 0, s, U, N, P, sel, theta, beta, out);
+  else hipLaunchKernelGGL(k_bulyan_coord<64>, g, b, 0, s, U, N, P, sel, theta, beta, out);
+  return (int)hipGetLastError();
+}
+
+// ============================================================================ geomed_weights
+// Geometric median (RFA, Pillutla et al.: smoothed Weiszfeld) of n <= 64 rows in Gram space: with w on the simplex and
+// z = sum_j w_j u_j, ||u_i - z||^2 = G_ii - 2 (G w)_i + w^T G w for the centred Gram G, so the iteration needs the rows
+// only for the final weighted sum.  Start w = alpha; an iteration computes d_i = sqrt(max(0, .)), the objective
+// sum_i alpha_i d_i and w_i <- alpha_i / max(nu, d_i), normalised; it stops after ``iters`` iterations or once
+// |objective - previous| <= 1e-9 objective.  One wave, lane i owns row i of G in LDS (row stride n_max + 1): G w is a
+// per-lane dot product in column order, w^T G w, the objective and the normaliser are xor-butterfly sums, which leave
+// the same bits on every lane (each step adds the same two operands on both partners), so the stop is wave-uniform.
+__global__ void __launch_bounds__(64) k_geomed_weights(const double* __restrict__ G, const double* __restrict__ alpha,
+                                                       int n, int iters, double nu, double* __restrict__ w,
+                                                       double* __restrict__ info) {
+  __shared__ double A[GMM_MAXN * KS_LD], wb[GMM_MAXN];
+  const int i = threadIdx.x;
+  for (int e = i; e < n * n; e += 64) {
+    const int r = e / n, c = e - r * n;
+    A[r * KS_LD + c] = G[e];
+  }
+  const double al = i < n ? alpha[i] : 0.0;
+  double wi = al, prev = INFINITY, obj = 0.0;
+  int it = 0;
+  __syncthreads();
+  const double gii = i < n ? A[i * KS_LD + i] : 0.0;
+  while (it < iters) {
+    wb[i] = wi;
+    __syncthreads();
+    double gw = 0.0;
+    if (i < n)
+      for (int j = 0; j < n; ++j) gw += A[i * KS_LD + j] * wb[j];
+    __syncthreads();  // (wb is rewritten by the next iteration)
+    const double q = wave_sum(wi * gw);
+    const double d2 = gii - 2.0 * gw + q;
+    const double d = i < n ? sqrt(d2 > 0.0 ? d2 : 0.0) : 0.0;
+    obj = wave_sum(al * d);
+    const double u = i < n ? al / (d > nu ? d : nu) : 0.0;
+    wi = u / wave_sum(u);
+    ++it;
+    if (fabs(obj - prev) <= 1e-9 * obj) break;  // (uniform: every lane holds the same obj and prev)
+    prev = obj;
+  }
+  if (i < n) w[i] = wi;
+  if (i == 0) {
+    info[0] = (double)it;
+    info[1] = obj;
+  }
+}
+
+int afl_geomed_weights(const double* G, const double* alpha, int n, int iters, double nu, double* w, double* info,
+                       hipStream_t s) {
+  if (n < 1 || n > GMM_MAXN || iters < 1 || !(nu > 0.0)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_geomed_weights, dim3(1), dim3(64), 0, s, G, alpha, n, iters, nu, w, info);
   return (int)hipGetLastError();
 }
