@@ -169,7 +169,7 @@ def shieldfl(U: torch.Tensor, sizes=None, **_) -> AggResult:
 
 def _centred_gram(U: torch.Tensor) -> torch.Tensor:
     """n x n Gram of the rows centred on their mean (fp64).  On the device: the fp64-MFMA Gram pass of
-    ``agg.hip`` (rows centred on row 0, then double-centred) instead of a generic fp64 GEMM with M = N = n and
+    ``agg.hip`` (rows centred on one of them, then double-centred) instead of a generic fp64 GEMM with M = N = n and
     K = P (~50 k), a shape the library GEMM handles poorly."""
     if U.is_cuda and 1 <= U.shape[0] <= 64:
         return ops.native().gram_centred(U.to(torch.float32).contiguous())[0]

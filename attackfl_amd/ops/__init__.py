@@ -104,8 +104,8 @@ def lie_candidate(G: torch.Tensor, z: float) -> torch.Tensor:
 
 
 def pairwise_sqdist(G: torch.Tensor) -> torch.Tensor:
-    """[K, K] fp64 squared L2 distances between rows.  Device: the centred Gram matrix on fp64 MFMA for
-    K <= 64 (``k_gram_f64``), the fp64 difference loop beyond."""
+    """[K, K] fp64 squared L2 distances between rows.  Device: the Gram matrix of the rows centred on a robustly
+    chosen row, on fp64 MFMA, for K <= 64 (``k_gram_f64``), the fp64 difference loop beyond (K <= 128)."""
     if _dev(G):
         if G.shape[0] <= 64:
             return native().pairwise_sqdist_gram(G.contiguous())

@@ -55,6 +55,7 @@ std::vector<torch::Tensor> colstats(torch::Tensor G, int64_t mode, double z) {
 
 torch::Tensor pairwise_sqdist(torch::Tensor G) {
   check_dev(G, "G", torch::kFloat32);
+  TORCH_CHECK(G.dim() == 2, "G must be [K, P]");
   const int K = G.size(0);
   const long P = G.size(1);
   auto D = torch::zeros({K, K}, G.options().dtype(torch::kFloat64));
@@ -62,12 +63,13 @@ torch::Tensor pairwise_sqdist(torch::Tensor G) {
   TORCH_CHECK(K <= 128, "pairwise_sqdist supports K <= 128 rows");
   const int M = K * (K - 1) / 2;
   auto partial = torch::empty({(long)afl_pair_sqdist_nblocks(P) * M}, D.options());
-  afl_pair_sqdist(G.data_ptr<float>(), K, P, partial.data_ptr<double>(), D.data_ptr<double>(), cur());
+  TORCH_CHECK(afl_pair_sqdist(G.data_ptr<float>(), K, P, partial.data_ptr<double>(), D.data_ptr<double>(), cur()) == 0,
+              "pairwise_sqdist launch failed");
   AFL_CHECK_LAUNCH();
   return D;
 }
 
-// pairwise squared distances through the centred Gram matrix on fp64 MFMA (K <= 64)
+// pairwise squared distances through the Gram matrix of the rows centred on a device-chosen row, fp64 MFMA (K <= 64)
 torch::Tensor pairwise_sqdist_gram(torch::Tensor G) {
   check_dev(G, "G", torch::kFloat32);
   TORCH_CHECK(G.dim() == 2 && G.size(0) >= 1 && G.size(0) <= 64, "G must be [K <= 64, P]");
@@ -173,7 +175,8 @@ std::vector<torch::Tensor> geomed_weights(torch::Tensor G, torch::Tensor alpha, 
 }
 
 // Gram matrix of the rows centred on the MEAN row (PCA of the updates: agg.fltracer / agg.gmm), through the same
-// fp64-MFMA pass (rows centred on row 0, H) followed by the double centring C = H - rowmean - colmean + mean
+// fp64-MFMA pass (H: the Gram of the rows centred on the pass's final centre row, the scratch tail) followed by the
+// double centring C = H - rowmean - colmean + mean, which does not depend on the centre beyond rounding
 std::vector<torch::Tensor> gram_centred(torch::Tensor G) {
   check_dev(G, "G", torch::kFloat32);
   TORCH_CHECK(G.dim() == 2 && G.size(0) >= 1 && G.size(0) <= 64, "G must be [K <= 64, P]");

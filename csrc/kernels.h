@@ -10,7 +10,7 @@ void afl_colstats(const float* G, int K, long P, float* mean, float* stdv, float
 void afl_weighted_rows(const float* U, const double* w, int N, long P, float* out, hipStream_t s,
                        const int* ok = nullptr, const float* fallback = nullptr);
 int afl_pair_sqdist_nblocks(long P);
-void afl_pair_sqdist(const float* G, int K, long P, double* partial, double* D, hipStream_t s);
+int afl_pair_sqdist(const float* G, int K, long P, double* partial, double* D, hipStream_t s);  // 0 or an error (2 <= K <= 128)
 void afl_seg_reduce(int mode, const float* X, long P, int rows, const float* mean, const float* dev, const int* tiles,
                     int T, const int* segf, int S, double* partial, double* out0, double* out1, hipStream_t s);
 void afl_coord_select(const float* U, int N, long P, int mode, int trim, float* out, hipStream_t s);

@@ -2,8 +2,9 @@
 //
 //   colstats        column mean / unbiased std (+ LIE candidate mean + z*std)      K-G2/K-G3
 //   weighted_rows   out = sum_i w_i U_i (fp64 weights, fp64 accumulate)            K-G1 FedAvg
-//   pair_sqdist     D2[i][j] = ||U_i - U_j||^2 (difference form, no cancellation)   K-G4b / Krum (K > 64)
-//   gram_f64        the same from the centred Gram matrix on fp64 MFMA               K-G4b / Krum (K <= 64)
+//   pair_sqdist     D2[i][j] = ||U_i - U_j||^2 (fp64 difference form, no cancellation) K-G4b / Krum (K > 64)
+//   gram_f64        the same from the Gram matrix of the rows centred on a robustly  K-G4b / Krum (K <= 64)
+//                   chosen row, on fp64 MFMA
 //   noise_philox    own + sigma * N(0,1) from Philox4x32-10 + Box-Muller             K-G10
 //   seg_reduce      per-(row, state_dict tensor) partial sums over tiles             K-G4a / K-G5
 //   coord_select    coordinate-wise lower median / trimmed mean (register sort)      K-G6
@@ -71,7 +72,10 @@ void afl_weighted_rows(const float* U, const double* w, int N, long P, float* ou
 
 // ============================================================================ pairwise sq-dist
 // Block b stages a [K][CH] column chunk in LDS (row stride CH+1: conflict-free column reads),
-// then threads loop over pairs; partial[b][pair] (fp64) is reduced by k_pair_reduce.
+// then threads loop over pairs; partial[b][pair] (fp64) is reduced by k_pair_reduce.  The difference and its
+// square are formed in fp64 (the difference of two fp32 values is exact there), so a distance carries only the
+// rounding of its fp64 sum: at most P * 2^-53 relative.  K <= 128: K * 257 * 4 bytes of LDS, above the 64 KB
+// default from K = 64 on (the launcher raises the kernel's dynamic-LDS limit).
 constexpr int PD_CH = 256;
 __global__ void __launch_bounds__(256) k_pair_sqdist(const float* __restrict__ G, int K, long P,
                                                      double* __restrict__ partial) {
@@ -92,8 +96,8 @@ __global__ void __launch_bounds__(256) k_pair_sqdist(const float* __restrict__ G
     const float* b = lds + j * (PD_CH + 1);
     double acc = 0.0;
     for (int t = 0; t < ncol; ++t) {
-      float d = a[t] - b[t];
-      acc += (double)(d * d);
+      const double d = (double)a[t] - (double)b[t];
+      acc += d * d;
     }
     partial[(long)blockIdx.x * M + pr] = acc;
   }
@@ -114,20 +118,39 @@ __global__ void k_pair_reduce(const double* __restrict__ partial, int nb, int K,
 
 int afl_pair_sqdist_nblocks(long P) { return afl_cdiv(P, PD_CH); }
 
-void afl_pair_sqdist(const float* G, int K, long P, double* partial, double* D, hipStream_t s) {
+int afl_pair_sqdist(const float* G, int K, long P, double* partial, double* D, hipStream_t s) {
+  if (K < 2 || K > 128 || P < 1) return (int)hipErrorInvalidValue;
   int nb = afl_cdiv(P, PD_CH);
   size_t lds = (size_t)K * (PD_CH + 1) * sizeof(float);
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)k_pair_sqdist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return -2;
   hipLaunchKernelGGL(k_pair_sqdist, dim3(nb), dim3(256), lds, s, G, K, P, partial);
   int M = K * (K - 1) / 2;
-  if (M > 0) hipLaunchKernelGGL(k_pair_reduce, dim3(afl_cdiv(M, 256)), dim3(256), 0, s, partial, nb, K, D);
+  hipLaunchKernelGGL(k_pair_reduce, dim3(afl_cdiv(M, 256)), dim3(256), 0, s, partial, nb, K, D);
+  return (int)hipGetLastError();
 }
 
 // ============================================================================ pairwise via Gram (MFMA)
-// D2[i][j] = ||G_i - G_j||^2 from the Gram matrix of the rows CENTRED on row 0 (X_i = G_i - G_0): the
-// difference-form correction — model updates are close to each other, so ||G_i||^2 + ||G_j||^2 - 2<G_i,G_j>
-// of the raw rows would cancel catastrophically, while the centred rows have norms of the order of the
-// distances themselves.  The products run on v_mfma_f64_16x16x4_f64 (fp32 inputs widened to fp64: exact
-// products, fp64 accumulation), so the result is as accurate as the fp64 difference loop above.
+// D2[i][j] = ||G_i - G_j||^2 = g_ii + g_jj - 2 g_ij from the Gram matrix g of the CENTRED rows X_i = G_i - G_c: the
+// difference-form correction — model updates are close to each other, so the Gram form of the raw rows would
+// cancel catastrophically, while rows centred on one of their own have norms of the order of the distances.
+// The centring is done in fp64 (the difference of two fp32 values: exact), the products run on
+// v_mfma_f64_16x16x4_f64 with fp64 accumulation.  Error model:
+//     err(D_ij) <~ eps64 * (|x_i|^2 + |x_j|^2),  x centred on the chosen row c
+// so D_ij is exact to fp64 rounding while x_i, x_j are not much longer than the distance itself, and loses
+// log2((|x_i|^2 + |x_j|^2) / D_ij) bits otherwise.  Two passes choose c:
+//   pass 1  c = 0.  Good when row 0 is a typical row; when client 0 is an outlier (a Random or scaled attack
+//           row) every benign x_i is huge and a benign-pair distance keeps only a few digits.
+//   pick    gram_pick_centre (the block of pass 1's reduction, at its end): c* = argmin_i lowermedian_{j != i}
+//           D1[i][j], ties to the lowest index — the row closest to the bulk, an outlier only when outliers are
+//           the majority; row 0 is kept while it is itself such a row.  Written to a device word: no host read,
+//           and a function of D1 alone, so the result stays bit-identical run to run.
+//   pass 2  the same kernels centred on c*, read from that word; its blocks return at once when c* == 0 and
+//           leave D and the Gram as pass 1 wrote them.
+// With a minority of outliers the result is exact to fp64 rounding for every pair.  It is NOT for two distant
+// tight clusters: whichever row is the centre, the other cluster's rows have |x|^2 of the order of the squared
+// cluster gap, and its within-cluster distances carry an absolute error of eps64 times that.
 // K <= 64 (T <= 4 row tiles of 16).  Block b covers GR_CH columns; each of its 4 waves a quarter of them,
 // 16 columns per step: lane l loads 4 consecutive columns of row (tile*16 + (l & 15)), column group l >> 4,
 // and issues 4 MFMAs per tile pair (element q of the 4 = MFMA q's k = l >> 4: the 16 columns are summed in a
@@ -137,8 +160,14 @@ typedef double d4v __attribute__((ext_vector_type(4)));
 
 template <int T>
 __global__ void __launch_bounds__(256) k_gram_f64(const float* __restrict__ G, int K, long P,
-                                                  double* __restrict__ partial) {
+                                                  const int* __restrict__ centre, double* __restrict__ partial) {
   constexpr int NP = T * (T + 1) / 2;
+  int crow = 0;  // pass 1 (centre == nullptr): row 0; pass 2: the picked row, nothing to do when that is row 0
+  if (centre != nullptr) {
+    crow = *centre;
+    if (crow <= 0 || crow >= K) return;  // (block-uniform)
+  }
+  const float* Gc = G + (long)crow * P;
   __shared__ double red[4][NP * 256];  // NP <= 10 tile pairs x 16 x 16
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r16 = lane & 15, grp = lane >> 4;
@@ -148,16 +177,16 @@ __global__ void __launch_bounds__(256) k_gram_f64(const float* __restrict__ G, i
   const long c_begin = (long)blockIdx.x * GR_CH + wave * (GR_CH / 4);
   for (int st = 0; st < GR_CH / 4 / 16; ++st) {
     const long c0 = c_begin + st * 16 + grp * 4;
-    float x[T][4];
-    float ctr[4];
+    double x[T][4];
+    double ctr[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) ctr[q] = c0 + q < P ? G[c0 + q] : 0.f;  // row 0 = the centre
+    for (int q = 0; q < 4; ++q) ctr[q] = c0 + q < P ? (double)Gc[c0 + q] : 0.0;  // the centre row
 #pragma unroll
     for (int t = 0; t < T; ++t) {
       const int row = t * 16 + r16;
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        x[t][q] = (row < K && c0 + q < P) ? G[(long)row * P + c0 + q] - ctr[q] : 0.f;
+        x[t][q] = (row < K && c0 + q < P) ? (double)G[(long)row * P + c0 + q] - ctr[q] : 0.0;
     }
     int p = 0;
 #pragma unroll
@@ -166,7 +195,7 @@ __global__ void __launch_bounds__(256) k_gram_f64(const float* __restrict__ G, i
       for (int tj = ti; tj < T; ++tj, ++p)
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-          acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)x[ti][q], (double)x[tj][q], acc[p], 0, 0, 0);
+          acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[ti][q], x[tj][q], acc[p], 0, 0, 0);
   }
   // fixed-order reduction over the 4 waves
 #pragma unroll
@@ -178,9 +207,75 @@ __global__ void __launch_bounds__(256) k_gram_f64(const float* __restrict__ G, i
     partial[(long)blockIdx.x * NP * 256 + e] = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
 }
 
-// sum the block partials in block order, then D2 = g_ii + g_jj - 2 g_ij (clamped at 0), symmetric, zero diagonal
+// The centre of pass 2 from pass 1's distances (the end of pass 1's k_gram_reduce, after D1 is formed): the row closest to
+// the bulk, c* = argmin_i lowermedian_{j != i} D1[i][j] (sorted position (K - 2) / 2 of the K - 1 values), ties to the
+// lowest index — except that row 0 stays the centre while its own median is within GR_KEEP0 times the smallest one:
+// it is then a typical row and pass 2 has nothing to do.  Why pass 1 is good enough then: with m0, mc the medians of
+// row 0 and of c*, each row has more than (K - 2) / 2 others within its median, so the two sets share a row j (or one
+// of 0, c* lies in the other's set) and sqrt(D_0c) <= sqrt(m0) + sqrt(mc) <= (sqrt(GR_KEEP0) + 1) sqrt(mc) = 3 sqrt(mc).
+// By the triangle inequality every row's length centred on row 0 is |x_i| <= sqrt(D_ci) + 3 sqrt(mc): the error
+// model's |x_i|^2 grow from D_ci to at most 2 D_ci + 18 mc, a constant factor for rows of the bulk and less for far
+// ones.  Row i of D1 sits in LDS (row stride K_max + 1); its median is found by rank counting (ties ranked by
+// column, so exactly one column has the wanted rank), the K columns of a row split over the block's four waves:
+// K^2 / 4 LDS reads per thread, about 1 k at K = 64, on every call (timings: profiles/bench_agg_edges.md); the argmin
+// is a butterfly on (median, index) in the first wave, read from lane 0.
+// NaN / inf rows (a faulted client).  Pass 1 always centres on row 0: if that row is not finite every Gram entry is
+// NaN, the clamp below turns all of D into zeros, no row is eligible, the word stays 0 and the result is what a
+// one-pass run gives (all zeros).  A non-finite row k != 0 has D[k][*] = 0 after the clamp in either pass; it is never
+// picked as PASS 2's centre (its own Gram entry is not finite) and its column is left out of the medians (+inf), so
+// the other rows' distances stay as accurate as without it.  The word is always in [0, K), and a function of D1 alone.
+constexpr int GR_MAXK = 64, GR_LD = GR_MAXK + 1;
+constexpr double GR_KEEP0 = 4.0;
+__device__ __forceinline__ bool gram_finite(double g) { return g == g && fabs(g) < INFINITY; }
+
+// every thread of the 256-thread block: row i = thread & 63 ranks the columns j = thread >> 6, + 4, ... (exactly one
+// column of a row has the wanted rank, so medv[i] has one writer); the first wave then takes the argmin
+__device__ void gram_pick_centre(const double* __restrict__ V, double* __restrict__ medv,
+                                 const double* __restrict__ gram, int K, int* __restrict__ centre) {
+  const int i = threadIdx.x & 63;
+  const bool mine = i < K && gram_finite(gram[i * K + i]);
+  if (mine) {
+    const double* v = V + i * GR_LD;
+    const int target = (K - 2) / 2;
+    for (int j = threadIdx.x >> 6; j < K; j += 4) {
+      if (j == i) continue;
+      const double x = v[j];
+      int rank = 0;
+#pragma unroll 8
+      for (int l = 0; l < K; ++l) rank += (l != i && (v[l] < x || (v[l] == x && l < j))) ? 1 : 0;
+      if (rank == target) medv[i] = x;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x >= 64) return;
+  const double med = mine ? medv[i] : INFINITY;
+  const double med0 = __shfl(med, 0, 64);
+  int bi = mine ? i : 64;
+  double bs = med;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double os = __shfl_xor(bs, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    const bool take = oi < 64 && (bi >= 64 || os < bs || (os == bs && oi < bi));
+    bs = take ? os : bs;
+    bi = take ? oi : bi;
+  }
+  bi = __shfl(bi, 0, 64);
+  bs = __shfl(bs, 0, 64);
+  if (i == 0) *centre = (bi > 0 && bi < K && !(med0 <= GR_KEEP0 * bs)) ? bi : 0;
+}
+
+// sum the block partials in block order, then D2 = g_ii + g_jj - 2 g_ij (clamped at 0), symmetric, zero diagonal.
+// Pass 1 (centre == nullptr) then picks pass 2's centre into *pick (when given); pass 2 (centre as in k_gram_f64)
+// returns at once when the picked row is row 0.
 __global__ void __launch_bounds__(256) k_gram_reduce(const double* __restrict__ partial, int nb, int K, int T,
-                                                     double* __restrict__ gram, double* __restrict__ D) {
+                                                     const int* __restrict__ centre, double* __restrict__ gram,
+                                                     double* __restrict__ D, int* __restrict__ pick) {
+  __shared__ double V[GR_MAXK * GR_LD], medv[GR_MAXK];
+  if (centre != nullptr) {
+    const int crow = *centre;
+    if (crow <= 0 || crow >= K) return;
+  }
   const int NP = T * (T + 1) / 2;
   for (int e = threadIdx.x; e < NP * 256; e += 256) {
     double a = 0.0;
@@ -198,27 +293,44 @@ __global__ void __launch_bounds__(256) k_gram_reduce(const double* __restrict__ 
   __syncthreads();
   for (int e = threadIdx.x; e < K * K; e += 256) {
     const int i = e / K, j = e % K;
-    const double d = i == j ? 0.0 : gram[i * K + i] + gram[j * K + j] - 2.0 * gram[i * K + j];
-    D[e] = d > 0.0 ? d : 0.0;
+    const double gjj = gram[j * K + j];
+    double d = i == j ? 0.0 : gram[i * K + i] + gjj - 2.0 * gram[i * K + j];
+    d = d > 0.0 ? d : 0.0;
+    D[e] = d;
+    V[i * GR_LD + j] = gram_finite(gjj) ? d : INFINITY;
   }
+  if (pick == nullptr) return;
+  if (threadIdx.x < GR_MAXK) medv[threadIdx.x] = INFINITY;
+  __syncthreads();
+  gram_pick_centre(V, medv, gram, K, pick);
 }
 
+// scratch (doubles): the block partials, one word for the picked centre, the K x K Gram of the final centre (tail)
 int afl_gram_partials(int K, long P) {
   const int T = (K + 15) / 16;
-  return afl_cdiv(P, GR_CH) * T * (T + 1) / 2 * 256 + K * K;
+  return afl_cdiv(P, GR_CH) * T * (T + 1) / 2 * 256 + 1 + K * K;
+}
+
+static void gram_pass(const float* G, int K, long P, int T, int nb, const int* centre, double* partial, double* gram,
+                      double* D, int* pick, hipStream_t s) {
+  switch (T) {
+    case 1: hipLaunchKernelGGL(k_gram_f64<1>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial); break;
+    case 2: hipLaunchKernelGGL(k_gram_f64<2>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial); break;
+    case 3: hipLaunchKernelGGL(k_gram_f64<3>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial); break;
+    default: hipLaunchKernelGGL(k_gram_f64<4>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial); break;
+  }
+  hipLaunchKernelGGL(k_gram_reduce, dim3(1), dim3(256), 0, s, partial, nb, K, T, centre, gram, D, pick);
 }
 
 int afl_pair_sqdist_gram(const float* G, int K, long P, double* partial, double* D, hipStream_t s) {
-  if (K < 1 || K > 64) return (int)hipErrorInvalidValue;
+  if (K < 1 || K > GR_MAXK || P < 1) return (int)hipErrorInvalidValue;
   const int T = (K + 15) / 16, nb = afl_cdiv(P, GR_CH);
-  switch (T) {
-    case 1: hipLaunchKernelGGL(k_gram_f64<1>, dim3(nb), dim3(256), 0, s, G, K, P, partial); break;
-    case 2: hipLaunchKernelGGL(k_gram_f64<2>, dim3(nb), dim3(256), 0, s, G, K, P, partial); break;
-    case 3: hipLaunchKernelGGL(k_gram_f64<3>, dim3(nb), dim3(256), 0, s, G, K, P, partial); break;
-    default: hipLaunchKernelGGL(k_gram_f64<4>, dim3(nb), dim3(256), 0, s, G, K, P, partial); break;
-  }
-  double* gram = partial + (long)nb * T * (T + 1) / 2 * 256;
-  hipLaunchKernelGGL(k_gram_reduce, dim3(1), dim3(256), 0, s, partial, nb, K, T, gram, D);
+  const long np = (long)nb * T * (T + 1) / 2 * 256;
+  int* centre = (int*)(partial + np);
+  double* gram = partial + np + 1;
+  // (K <= 2: every row is as central as row 0, one pass)
+  gram_pass(G, K, P, T, nb, nullptr, partial, gram, D, K > 2 ? centre : nullptr, s);
+  if (K > 2) gram_pass(G, K, P, T, nb, centre, partial, gram, D, nullptr, s);
   return (int)hipGetLastError();
 }
 
@@ -331,20 +443,29 @@ void afl_seg_reduce(int mode, const float* X, long P, int rows, const float* mea
 // ============================================================================ coordinate select
 // Each thread owns one column: N values in registers, odd-even transposition sort network with
 // compile-time indices (NMAX template; padding +inf), then lower-median or trimmed mean.
+// NaN (the engine marks a faulted client's row with it) follows the composites: torch.median returns NaN for a
+// column that holds one; torch.sort places NaN last, so the trimmed mean is NaN when the column holds more NaNs
+// than ``trim`` and the mean of the real values at [trim, N - trim) otherwise.  The column's NaNs are counted
+// while loading; the sort moves them behind everything, the +inf padding included, so with at most ``trim`` of
+// them the summed positions hold real values.
 template <int NMAX>
 __global__ void __launch_bounds__(256) k_coord_select(const float* __restrict__ U, int N, long P, int mode, int trim,
                                                       float* __restrict__ out) {
   long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= P) return;
   float v[NMAX];
+  int nnan = 0;
 #pragma unroll
-  for (int i = 0; i < NMAX; ++i) v[i] = i < N ? U[(long)i * P + c] : __int_as_float(0x7f800000);
+  for (int i = 0; i < NMAX; ++i) {
+    v[i] = i < N ? U[(long)i * P + c] : __int_as_float(0x7f800000);
+    nnan += v[i] != v[i] ? 1 : 0;
+  }
 #pragma unroll
   for (int r = 0; r < NMAX; ++r) {
 #pragma unroll
     for (int i = (r & 1); i + 1 < NMAX; i += 2) {
       float a = v[i], b = v[i + 1];
-      // NaN-aware: torch.sort/median place NaN last (treated as largest)
+      // NaN-aware: a NaN is treated as the largest value (behind the +inf padding)
       bool sw = (a > b) || (a != a && b == b);
       v[i] = sw ? b : a;
       v[i + 1] = sw ? a : b;
@@ -355,11 +476,12 @@ __global__ void __launch_bounds__(256) k_coord_select(const float* __restrict__ 
     const int mid = (N - 1) / 2;
 #pragma unroll
     for (int i = 0; i < NMAX; ++i) r = (i == mid) ? v[i] : r;
+    if (nnan > 0) r = __int_as_float(0x7fc00000);
   } else {
     float acc = 0.f;
 #pragma unroll
     for (int i = 0; i < NMAX; ++i) acc += (i >= trim && i < N - trim) ? v[i] : 0.f;
-    r = acc / (float)(N - 2 * trim);
+    r = nnan > trim ? __int_as_float(0x7fc00000) : acc / (float)(N - 2 * trim);
   }
   out[c] = r;
 }
@@ -988,7 +1110,7 @@ int afl_krum_select(const double* D, int n, int f, int rounds, int iterated, int
 // ============================================================================ bulyan_coord
 // Bulyan's coordinate step: per column, over the theta rows sel[0 .. theta) of U (a device index list: no gathered
 // copy of the rows), the mean of the beta values closest to the lower median (sorted position (theta - 1) / 2, as
-// coord_select's median).  One thread per column, the k_coord_select register sort (NaN last), then a two-pointer
+// coord_select's median).  One thread per column, the k_coord_select register sort (NaN last, counted), then a two-pointer
 // expansion from the median position: the beta smallest keys (|x - med| in fp32, x) are contiguous in sorted order, and
 // on an equal distance the left neighbour, the smaller value, is taken.  Registers are only indexed by compile-time
 // constants (the neighbours come out of predicated sweeps), the window is summed in fp64 in sorted order.
@@ -1000,6 +1122,7 @@ __global__ void __launch_bounds__(256) k_bulyan_coord(const float* __restrict__ 
   long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= P) return;
   float v[NMAX];
+  int nnan = 0;
 #pragma unroll
   for (int i = 0; i < NMAX; ++i) {
     float x = __int_as_float(0x7f800000);
@@ -1008,6 +1131,7 @@ __global__ void __launch_bounds__(256) k_bulyan_coord(const float* __restrict__ 
       x = U[(long)r * P + c];
     }
     v[i] = x;
+    nnan += x != x ? 1 : 0;
   }
 #pragma unroll
   for (int r = 0; r < NMAX; ++r) {
@@ -1023,6 +1147,10 @@ __global__ void __launch_bounds__(256) k_bulyan_coord(const float* __restrict__ 
   float med = 0.f;
 #pragma unroll
   for (int i = 0; i < NMAX; ++i) med = (i == mid) ? v[i] : med;
+  // NaN as composite.bulyan_coord (torch.sort: NaN last, a NaN distance last): the window runs over the ``real``
+  // non-NaN values only; beta > real gives NaN; a NaN median (mid >= real) makes every distance NaN, and the stable
+  // sort of those keeps the beta smallest values
+  const int real = theta - nnan;
   int lo = mid, hi = mid;
   for (int s = 1; s < beta; ++s) {
     float a = 0.f, b = 0.f;  // the neighbours v[lo - 1], v[hi + 1]
@@ -1031,15 +1159,19 @@ __global__ void __launch_bounds__(256) k_bulyan_coord(const float* __restrict__ 
       a = (i == lo - 1) ? v[i] : a;
       b = (i == hi + 1) ? v[i] : b;
     }
-    const bool left = lo > 0 && (hi + 1 >= theta || fabsf(a - med) <= fabsf(b - med));
-    // (beta <= theta: one side is inside the list while the window is short; a NaN distance goes right first)
-    if (left || hi + 1 >= theta) lo = max(lo - 1, 0);
+    const bool left = lo > 0 && (hi + 1 >= real || fabsf(a - med) <= fabsf(b - med));
+    // (beta <= real: one side is inside the list while the window is short)
+    if (left || hi + 1 >= real) lo = max(lo - 1, 0);
     else ++hi;
+  }
+  if (mid >= real) {
+    lo = 0;
+    hi = beta - 1;
   }
   double acc = 0.0;
 #pragma unroll
   for (int i = 0; i < NMAX; ++i) acc += (i >= lo && i <= hi) ? (double)v[i] : 0.0;
-  out[c] = (float)(acc / (double)beta);
+  out[c] = beta > real ? __int_as_float(0x7fc00000) : (float)(acc / (double)beta);
 }
 
 int afl_bulyan_coord(const float* U, int N, long P, const int* sel, int theta, int beta, float* out, hipStream_t s) {
