@@ -16,25 +16,23 @@ Each rule returns ``AggResult(params [P] | None, ok, info)``.  Rows are in clien
 * fltracer      ``src/Utils.py:359-369`` (dormant in the reference)  PCA(1) + MAD z-score
 * byzantine     ``src/Utils.py:218-248`` (dead code in the reference) cosine ≥ 0.9 to model 0
 Beyond the reference (docs/PARITY.md): multi_krum, bulyan (assumed Byzantine count ``byz-f``) and geomed (RFA).
-FLTrust and the hypernetwork live in ``fl/server.py`` (they need training).
+FLTrust and the hypernetwork live in the engine (``fl/engine.py`` ``_fltrust``, ``fl/hyper_server.py``): they train.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Dict, Optional
+from typing import Dict, Optional, Union
 
-import math
-
-import numpy as np
 import torch
 
 from .. import ops
+from ..ops.composite import gmm_filter_ref  # noqa: F401  (the kernel's host mirror: tools and tests import it here)
 
 
 @dataclass
 class AggResult:
     params: Optional[torch.Tensor]
-    ok: bool = True
+    ok: Union[bool, torch.Tensor] = True  # a 0-d device bool where the rule decides on the device (gmm)
     info: Dict = field(default_factory=dict)
 
 
@@ -152,7 +150,7 @@ def geomed(U: torch.Tensor, sizes=None, geomed_iters: int = 100, geomed_nu: floa
     n = U.shape[0]
     a = torch.ones(n, dtype=torch.float64) if sizes is None else sizes
     a = _device_weights(a, U.device)
-    w, iters, obj = ops.geomed_weights(_centred_gram(U), a / a.sum(), int(geomed_iters), float(geomed_nu))
+    w, iters, obj = ops.geomed_weights(ops.centred_gram(U), a / a.sum(), int(geomed_iters), float(geomed_nu))
     return AggResult(ops.weighted_rows(U, w), True, {"weights": w, "iters": iters, "objective": obj})
 
 
@@ -167,214 +165,24 @@ def shieldfl(U: torch.Tensor, sizes=None, **_) -> AggResult:
     return AggResult(ops.weighted_rows(U, w.double()), True, {"weights": w, "cos": cos})
 
 
-def _centred_gram(U: torch.Tensor) -> torch.Tensor:
-    """n x n Gram of the rows centred on their mean (fp64).  On the device: the fp64-MFMA Gram pass of
-    ``agg.hip`` (rows centred on one of them, then double-centred) instead of a generic fp64 GEMM with M = N = n and
-    K = P (~50 k), a shape the library GEMM handles poorly."""
-    if U.is_cuda and 1 <= U.shape[0] <= 64:
-        return ops.native().gram_centred(U.to(torch.float32).contiguous())[0]
-    X = U.double()
-    Xc = X - X.mean(dim=0, keepdim=True)
-    return Xc @ Xc.t()
-
-
-def _gmm_chol(S, r):
-    Lc = np.zeros((4, 4))
-    for i in range(r):
-        for j in range(i + 1):
-            s = S[i][j]
-            for k in range(j):
-                s -= Lc[i][k] * Lc[j][k]
-            if i == j:
-                if not s > 0.0:
-                    return None
-                Lc[i][i] = math.sqrt(s)
-            else:
-                Lc[i][j] = s / Lc[j][j]
-    return Lc
-
-
-def _gmm_md2(Lc, r, x, mu):
-    y = [0.0] * r
-    s = 0.0
-    for i in range(r):
-        v = x[i] - mu[i]
-        for k in range(i):
-            v -= Lc[i][k] * y[k]
-        y[i] = v / Lc[i][i]
-        s += y[i] * y[i]
-    return s
-
-
-def gmm_filter_ref(G: np.ndarray, att: np.ndarray, rank: Optional[int] = None):
-    """Host mirror of ``agg.hip`` ``k_gmm_filter`` (same algorithm and operation order, fp64): returns
-    (keep [n] bool, threshold, kept, ok).  See the kernel for the algorithm and its reference mapping.
-    ``rank`` > 0 sets the PCA rank r = min(rank, 4, n); None / 0: r = max(1, min(4, n // 2 - 1)) (the
-    sensitivity study: profiles/gmm_rank_study_r6.md)."""
-    n = G.shape[0]
-    A = [list(map(float, row)) for row in G]
-    V = [[1.0 if i == j else 0.0 for j in range(n)] for i in range(n)]
-    for _ in range(12):
-        for p in range(n - 1):
-            for q in range(p + 1, n):
-                apq = A[p][q]
-                if abs(apq) < 1e-300:
-                    continue
-                th = (A[q][q] - A[p][p]) / (2.0 * apq)
-                t = (1.0 if th >= 0.0 else -1.0) / (abs(th) + math.sqrt(th * th + 1.0))
-                c = 1.0 / math.sqrt(t * t + 1.0)
-                sn = t * c
-                for k in range(n):
-                    akp, akq = A[k][p], A[k][q]
-                    A[k][p] = c * akp - sn * akq
-                    A[k][q] = sn * akp + c * akq
-                for k in range(n):
-                    apk, aqk = A[p][k], A[q][k]
-                    A[p][k] = c * apk - sn * aqk
-                    A[q][k] = sn * apk + c * aqk
-                for k in range(n):
-                    vkp, vkq = V[k][p], V[k][q]
-                    V[k][p] = c * vkp - sn * vkq
-                    V[k][q] = sn * vkp + c * vkq
-    order = sorted(range(n), key=lambda i: -A[i][i])  # stable: ties keep index order (as the insertion sort)
-    ev = [A[i][i] for i in order]
-    r = min(int(rank), 4, n) if rank else max(1, min(4, n // 2 - 1))
-    Z = [[V[i][order[k]] * math.sqrt(max(ev[k], 1e-30)) for k in range(r)] for i in range(n)]
-    zmax = max(1e-30, max(abs(z) for row in Z for z in row))
-    Z = [[z / zmax for z in row] for row in Z]
-    idx = [i for i in range(n) if not att[i]]
-    nb = len(idx)
-    idx += [i for i in range(n) if att[i]]
-    X = [Z[i] for i in idx]
-    m = len(X)
-    K = 2 if m >= 2 else 1
-    mu = [list(X[0]), list(X[0])]
-    resp = [[1.0, 0.0] for _ in range(m)]
-    if K == 2:
-        far, best = 0, -1.0
-        for i in range(m):
-            d = sum((X[i][k] - X[0][k]) * (X[i][k] - X[0][k]) for k in range(r))
-            if d > best:
-                best, far = d, i
-        mu[1] = list(X[far])
-        for _ in range(10):
-            s = [[0.0] * r, [0.0] * r]
-            cnt = [0.0, 0.0]
-            for i in range(m):
-                d0 = d1 = 0.0
-                for k in range(r):
-                    d0 += (X[i][k] - mu[0][k]) * (X[i][k] - mu[0][k])
-                    d1 += (X[i][k] - mu[1][k]) * (X[i][k] - mu[1][k])
-                lab = 1 if d1 < d0 else 0
-                resp[i] = [1.0 if lab == 0 else 0.0, 1.0 if lab == 1 else 0.0]
-                cnt[lab] += 1.0
-                for k in range(r):
-                    s[lab][k] += X[i][k]
-            for cc in range(2):
-                if cnt[cc] > 0.0:
-                    mu[cc] = [s[cc][k] / cnt[cc] for k in range(r)]
-    eps10, reg, LOG2PI = 10.0 * 2.220446049250313e-16, 1e-6, 1.8378770664093453
-    st = {"w": [0.0, 0.0], "Lc": [None, None], "logdet": [0.0, 0.0], "ok": True}
-
-    def mstep():
-        nks = 0.0
-        for cc in range(K):
-            nk = eps10
-            for i in range(m):
-                nk += resp[i][cc]
-            for k in range(r):
-                sm = 0.0
-                for i in range(m):
-                    sm += resp[i][cc] * X[i][k]
-                mu[cc][k] = sm / nk
-            cov = [[0.0] * 4 for _ in range(4)]
-            for a_ in range(r):
-                for b_ in range(r):
-                    sm = 0.0
-                    for i in range(m):
-                        sm += resp[i][cc] * (X[i][a_] - mu[cc][a_]) * (X[i][b_] - mu[cc][b_])
-                    cov[a_][b_] = sm / nk + (reg if a_ == b_ else 0.0)
-            st["w"][cc] = nk
-            nks += nk
-            Lc = _gmm_chol(cov, r)
-            if Lc is None:
-                st["ok"] = False
-                Lc = np.eye(4)
-            st["Lc"][cc] = Lc
-            st["logdet"][cc] = 2.0 * sum(math.log(Lc[k][k]) for k in range(r))
-        for cc in range(K):
-            st["w"][cc] /= nks
-
-    def wlogp(x, cc):
-        return math.log(st["w"][cc]) - 0.5 * (r * LOG2PI + _gmm_md2(st["Lc"][cc], r, x, mu[cc]) + st["logdet"][cc])
-
-    mstep()
-    lb = -math.inf
-    it = 0
-    while it < 100 and st["ok"]:
-        prev = lb
-        tot = 0.0
-        for i in range(m):
-            lp = [wlogp(X[i], 0), wlogp(X[i], 1) if K == 2 else -math.inf]
-            mx = max(lp)
-            lse = mx + math.log(math.exp(lp[0] - mx) + math.exp(lp[1] - mx))
-            tot += lse
-            resp[i] = [math.exp(lp[0] - lse), math.exp(lp[1] - lse) if K == 2 else 0.0]
-        mstep()
-        lb = tot / m
-        it += 1
-        if abs(lb - prev) < 1e-3:
-            break
-    mds = [math.sqrt(_gmm_md2(st["Lc"][0], r, X[i], mu[0])) for i in range(nb)]
-    if nb:
-        mb = sum(mds) / nb
-        thr = 3.0 * math.sqrt(sum((d - mb) ** 2 for d in mds) / nb)
-    else:
-        thr = math.inf
-    keep = np.zeros(n, dtype=bool)
-    for i in range(n):
-        cc = 1 if (K == 2 and wlogp(Z[i], 1) > wlogp(Z[i], 0)) else 0
-        keep[i] = st["ok"] and math.sqrt(_gmm_md2(st["Lc"][cc], r, Z[i], mu[cc])) <= thr
-    return keep, thr, int(keep.sum()), st["ok"]
-
-
 def gmm(U: torch.Tensor, sizes=None, attackers: Optional[torch.Tensor] = None, seed: int = 0,
         gmm_rank: Optional[int] = None, **_) -> AggResult:
     """GMM gradient filter (reference server.py:352-370; its full-covariance fit on raw P-dim updates crashes, A-8):
-    a 2-component GMM on the updates' leading PCA scores, deterministic (agg.hip ``k_gmm_filter``, one fused
-    launch on the device; ``gmm_filter_ref`` on the host).  The mean of the kept rows; the round fails when no
-    row is kept (reference ``round_result = False``) — the only host read of the mode, one byte after the kernel.
-    ``gmm_rank``: the PCA rank (engine ``gmm-rank``; None / 0 = max(1, min(4, n // 2 - 1)))."""
+    a 2-component GMM on the updates' leading PCA scores, deterministic (``ops.gmm_filter``: one fused launch on
+    the device, its mirror on the host).  The mean of the kept rows; the round fails when no row is kept (reference
+    ``round_result = False``).  Device, n <= 64: no host read, ``ok`` is a 0-d device bool (and ``params`` the mean
+    of all rows when none is kept) — the caller reads it where it waits anyway; ``attackers`` on the host or the
+    device.  ``gmm_rank``: the PCA rank (engine ``gmm-rank``; None / 0 = max(1, min(4, n // 2 - 1)))."""
     n = U.shape[0]
-    att = attackers.bool() if attackers is not None else torch.zeros(n, dtype=torch.bool)
-    G = _centred_gram(U)
+    att = attackers if attackers is not None else torch.zeros(n, dtype=torch.bool)
+    keep, inf = ops.gmm_filter(ops.centred_gram(U), att, int(gmm_rank or 0))
     if U.is_cuda and n <= 64:
-        keep_d, inf_d = ops.native().gmm_filter(G.contiguous(), att.to(U.device, torch.uint8).contiguous(),
-                                                int(gmm_rank or 0))
-        keep = keep_d.bool()
-        thr = inf_d[0]
-        if not bool(inf_d[1] > 0):  # (the one synchronising read)
-            return AggResult(None, False, {"kept": keep, "threshold": thr})
-        return AggResult(_masked_mean(U, keep), True, {"kept": keep, "threshold": thr})
-    keep, thr, kept, _ = gmm_filter_ref(G.cpu().numpy(), att.cpu().numpy(), rank=gmm_rank)
-    if not kept:
+        return AggResult(_masked_mean(U, keep), inf[1] > 0, {"kept": keep, "threshold": inf[0]})
+    # the host form keeps the sum over the kept rows only: in fp32 it differs from the masked sum in the last bit
+    idx = torch.nonzero(keep).reshape(-1)
+    if not idx.numel():
         return AggResult(None, False, {"kept": []})
-    return AggResult(mean_of(U[torch.from_numpy(np.nonzero(keep)[0]).to(U.device)]), True,
-                     {"kept": np.nonzero(keep)[0].tolist(), "threshold": float(thr)})
-
-
-def gmm_early(U: torch.Tensor, attackers: torch.Tensor, gmm_rank: Optional[int] = None):
-    """``gmm`` without its host read, for the engine's early launch (device U, n <= 64): (mean of the kept
-    rows, device bool "some row kept" = the rule's success, info).  ``attackers``: bool, host or device (a host
-    tensor goes up pinned, never through a pageable copy that would wait for the stream)."""
-    from ..ops.layers import upload
-
-    att = attackers.to(torch.uint8)
-    att = upload(att, U.device) if att.device.type == "cpu" else att
-    G = _centred_gram(U)
-    keep_d, inf_d = ops.native().gmm_filter(G.contiguous(), att.contiguous(), int(gmm_rank or 0))
-    keep = keep_d.bool()
-    return _masked_mean(U, keep), inf_d[1] > 0, {"kept": keep, "threshold": inf_d[0]}
+    return AggResult(mean_of(U[idx]), True, {"kept": idx.tolist(), "threshold": float(inf[0])})
 
 
 def scionfl(U: torch.Tensor, sizes: torch.Tensor, seed: int = 0, **_) -> AggResult:
@@ -409,18 +217,15 @@ def _median(x: torch.Tensor) -> torch.Tensor:
     return 0.5 * (s[(n - 1) // 2] + s[n // 2])
 
 
+_centred_gram = ops.centred_gram  # (the name tools and tests know)
+
+
 def _top_pc_scores(U: torch.Tensor, sweeps: int = 12) -> torch.Tensor:
     """First principal-component scores of the rows (sklearn ``PCA(1).fit_transform`` up to the sign) with no
-    host synchronisation: the n x n Gram of the centred rows, its leading eigenpair by a fixed-sweep Jacobi
-    eigen-decomposition on the device (``k_top_pc``, n <= 64; ``torch.linalg.eigh`` on the CPU / larger n),
+    host synchronisation: the leading eigenpair of the n x n Gram of the centred rows (``ops.top_pc``),
     score = v sqrt(lambda).  Exact for any spectrum gap (repeated squaring, the round-4 form, let the second
     eigenvector leak in when the top two eigenvalues are close)."""
-    G = _centred_gram(U)
-    n = G.shape[0]
-    if G.is_cuda and n <= 64:
-        return ops.native().top_pc(G.contiguous(), int(sweeps))
-    ev, V = torch.linalg.eigh(G)
-    return V[:, -1] * torch.sqrt(ev[-1].clamp_min(0.0))
+    return ops.top_pc(ops.centred_gram(U), sweeps)
 
 
 def fltracer(U: torch.Tensor, sizes: torch.Tensor, threshold: float = 2.5, **_) -> AggResult:

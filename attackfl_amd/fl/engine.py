@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..agg import AGGREGATORS, AggResult, gmm_early
+from ..agg import AGGREGATORS, AggResult
 from ..agg import host_info as agg_host_info
 from ..attacks import DistanceEngine, host_info, run_attack
 from ..config import AttackSpec, Config
@@ -50,12 +50,10 @@ from ..utils.log import Logger, MetricsWriter, NullLogger, print_with_color
 from .hyper_server import HyperServer
 from .trainers import Plan, make_plan, make_trainer
 
-# rules that run on the device without a host read: with one of them the aggregate and the next round's launch
-# are enqueued before the host waits for the training, as for FedAvg (FLEngine._early_launch).  gmm (whose
-# success the host reads after its wait, from a copy queued before the next launch) and FLTrust (server-model
-# training + trust weights, device work too) take the early launch through branches of their own
-EARLY_AGGREGATORS = ("trimmed_mean", "median", "krum", "shieldfl", "scionfl", "fltracer", "byzantine", "multi_krum",
-                     "bulyan", "geomed")
+# every rule of AGGREGATORS runs on the device without a host read (gmm up to 64 rows; its success is a device
+# bool): with one of them the aggregate and the next round's launch are enqueued before the host waits for the
+# training, as for FedAvg, FLTrust and the native hypernetwork update (FLEngine._early_ok, _early_launch)
+EARLY_AGGREGATORS = tuple(m for m in AGGREGATORS if m != "fedavg")
 
 META = 5  # valid, result, size, is_attacker, decision word; then the client's per-epoch losses (E columns)
 DECISION = 4  # column of the sender's decision word (``FLEngine._decision_word``)
@@ -149,6 +147,21 @@ def build_client_table(cfg: Config, world: int, attackers: Optional[Dict[int, At
         uid = str(uuid.UUID(int=(seed * 1000003 + c + 1) & ((1 << 128) - 1), version=4))
         table.append(ClientInfo(c, uid, owner, atk.get(c)))
     return table
+
+
+@dataclass
+class EarlyLaunch:
+    """An early launch (``FLEngine._early_launch``): what its server step reported and what undoing it needs."""
+    g_old: Optional[torch.Tensor]            # the global model before the step
+    fl_old: Optional[torch.Tensor]           # FLTrust's server model before the step
+    hyper_step: Optional[int]                # the hypernetwork's step count before the step
+    snap: tuple                              # (per local client (rng state, training round, genuine), server rng state)
+    prep: Optional[dict]                     # the next launch's host half, staged ahead
+    info: dict = field(default_factory=dict)  # the server step's info
+    rule_ok: Optional[tuple] = None          # gmm: (pinned bool, event) of the filter's success
+    keep: Optional[List[int]] = None         # with attackers: the genuine rows stored, and the pool made of them
+    pool: Optional[torch.Tensor] = None
+    agg_done: Optional["torch.cuda.Event"] = None
 
 
 _LIVE: "weakref.WeakSet[FLEngine]" = weakref.WeakSet()
@@ -269,8 +282,6 @@ class FLEngine:
         self._spec = None
         self._next_prep = None  # the next launch's host half, staged while the current training runs
         self._fedavg_w = None
-        self._early_agg_info: dict = {}  # a robust rule's info of the last early launch (_early_info)
-        self._early_agg_ok = None  # gmm: (pinned bool, event) of the early launch's filter success
         self._val_stream = None
         self._start_ready = None
         self._sel_cache = None
@@ -784,42 +795,69 @@ class FLEngine:
     # SERVER
     # ------------------------------------------------------------------------------------------
     def _rule_args(self) -> dict:
-        """The engine keys of multi_krum / bulyan (``byz-f``) and geomed (``geomed-iters``, ``geomed-nu``)."""
+        """The keywords every rule receives (each reads its own): the round's seed (scionfl), ``gmm-rank``, ``byz-f``
+        (multi_krum / bulyan), ``geomed-iters`` and ``geomed-nu``."""
         e = self.cfg.engine
-        return {"byz_f": e.get("byz-f", "auto"), "geomed_iters": int(e.get("geomed-iters", 100)),
+        return {"seed": self.seed * 13 + self.round_no, "gmm_rank": int(e.get("gmm-rank", 1)),
+                "byz_f": e.get("byz-f", "auto"), "geomed_iters": int(e.get("geomed-iters", 100)),
                 "geomed_nu": float(e.get("geomed-nu", 1e-6))}
 
-    def _aggregate(self, U: torch.Tensor, sizes: torch.Tensor, attackers: torch.Tensor, round_ok: bool) -> dict:
-        info: dict = {}
-        if not round_ok:
-            return info
-        mode = self.mode
+    def _server_step(self, U: torch.Tensor, sizes: torch.Tensor, attackers: torch.Tensor,
+                     ok_all: Optional[torch.Tensor], w: Optional[torch.Tensor] = None, gen_key=None):
+        """The server rule of ``self.mode`` on the update rows ``U`` — the only place that maps the mode to work.
+        ``ok_all`` None: the host knows that every client succeeded (the serial path, ``_aggregate``).  A 0-d device
+        bool, "every client succeeded" as the device knows it (``_early_launch``): nothing is read back, the new
+        global model is ``where(ok_all [& the rule's success], new, old)`` and the hypernetwork update gets it as
+        ``enable``; FedAvg also takes the clients' int32 success flags themselves and reduces them inside its own
+        pass.  ``w``: FedAvg weights already on the device (each caller keeps its own source); ``gen_key``: the clients
+        whose next START models the hypernetwork update generates.  Returns (info, the rule's own success: None =
+        always, or a 0-d tensor — gmm).  What a failed early round rolls back stays on ``self`` (``fltrust_model``,
+        ``_trust``, ``_fl_pending``, ``hyper.step``: ``_early_launch_failed``)."""
+        mode, g_old = self.mode, self.global_params
         if mode == "hyper":
-            ups = {i: U[k] for k, i in enumerate(self.selected)}
             self.ckpt_writer.fence()  # the previous round's checkpoint copy of the arena, updated in place below
-            self.hyper.train(self.selected, ups)
-            info["_lazy"] = lambda: self.hyper.last_info  # read after validation: no sync between them
-            return info
+            # (a device ok_all: the update runs, or leaves the hypernetwork untouched, as the device decides)
+            kw = {} if ok_all is None else {"enable": ok_all.to(torch.int32).reshape(1), "gen_key": gen_key}
+            self.hyper.train(self.selected, {i: U[k] for k, i in enumerate(self.selected)}, **kw)
+            return {"_lazy": lambda: self.hyper.last_info}, None  # read after validation: no sync between them
         if mode == "FLTrust":
-            self.global_params = self._fltrust(U)
-            return info
-        if mode == "fedavg" and self._fedavg_w is not None and U.shape[0] == self._fedavg_w.shape[0] and U.is_cuda:
+            new = self._fltrust(U)
+            self.global_params = new if ok_all is None else torch.where(ok_all, new, g_old)
+            return {}, None
+        if mode == "fedavg" and w is not None:
             # the weights were staged with the launch (sizes known then): no host -> device copy here
-            self.global_params = ops.weighted_rows(U, self._fedavg_w)
-            info["n"] = int(U.shape[0])
-            return info
-        fn = AGGREGATORS[mode]
-        res: AggResult = fn(U, sizes, attackers=attackers, seed=self.seed * 13 + self.round_no,
-                            gmm_rank=int(self.cfg.engine.get("gmm-rank", 1)), **self._rule_args())
-        info.update({k: v for k, v in res.info.items() if k != "scores"})
-        if not res.ok:
-            info["agg_failed"] = True
-        elif res.params is not None:
-            g = res.params.to(torch.float32)
-            if g.untyped_storage().data_ptr() == U.untyped_storage().data_ptr():
-                g = g.clone()  # a selected row (e.g. Krum) of U, which may be the live client models
-            self.global_params = g
-        return info
+            if ok_all is None:
+                self.global_params = ops.weighted_rows(U, w)
+            elif ok_all.dim():
+                self.global_params = ops.weighted_rows(U, w, ok_all, g_old)  # (the success check fused into the pass)
+            else:
+                self.global_params = torch.where(ok_all, ops.weighted_rows(U, w), g_old)
+            return {"n": int(U.shape[0])}, None
+        res: AggResult = AGGREGATORS[mode](U, sizes, attackers=attackers, **self._rule_args())
+        info = {k: v for k, v in res.info.items() if k != "scores"}
+        if ok_all is None:
+            if not bool(res.ok):  # (gmm on the device: a 0-d tensor, the serial path's one synchronising read)
+                info["agg_failed"] = True
+            elif res.params is not None:
+                g = res.params.to(torch.float32)
+                if g.untyped_storage().data_ptr() == U.untyped_storage().data_ptr():
+                    g = g.clone()  # a selected row (e.g. Krum) of U, which may be the live client models
+                self.global_params = g
+            return info, None
+        rule_ok = None if res.ok is True else torch.as_tensor(res.ok, device=U.device)
+        if res.params is not None:  # (a new tensor: never a row of U)
+            self.global_params = torch.where(ok_all if rule_ok is None else ok_all & rule_ok,
+                                             res.params.to(torch.float32), g_old)
+        return info, rule_ok
+
+    def _aggregate(self, U: torch.Tensor, sizes: torch.Tensor, attackers: torch.Tensor, round_ok: bool) -> dict:
+        """The serial path: the host has read the round's meta."""
+        if not round_ok:
+            return {}
+        w = self._fedavg_w  # (one rank, every row stored; the several-rank serial path weighs by the host sizes)
+        if w is not None and not (U.is_cuda and U.shape[0] == w.shape[0]):
+            w = None
+        return self._server_step(U, sizes, attackers, None, w=w)[0]
 
     def _fltrust_setup(self):
         """Root set (first 200 test rows, ``server.py:290-293``), its device table and the server model's
@@ -911,20 +949,12 @@ class FLEngine:
         t1 = time.perf_counter()
         P = self.P
         snapshot = None
-        attackers = None
         stored = len(self.selected)
         if esl is not None:
-            # FedAvg, one rank: the aggregate and the next launch went in before the wait (_early_launch)
+            # one rank: the aggregate and the next launch went in before the wait (_early_launch)
             U = None
             meta = torch.from_numpy(self._meta_host[self._local_rows()])
-            results = meta.numpy()[:, 1] > 0.5
-            round_ok = bool(results.all())
-            info = self._early_info(round_ok)
-            if not self._early_agg_done() and round_ok:
-                round_ok = False
-                info = {**self._early_agg_info, "agg_failed": True}
-            if not round_ok:
-                self._early_launch_failed(esl, results)
+            round_ok, info = self._early_outcome(esl, meta.numpy()[:, 1] > 0.5)
             t2 = t3 = time.perf_counter()
         elif self.fast_fedavg:
             U = None
@@ -976,12 +1006,7 @@ class FLEngine:
             snapshot = self.hyper.snapshot() if (self.mode == "hyper" and self.cfg.hyper_detection.get("enable")) \
                 else None
             if esl is not None:  # (several ranks: the aggregate and the next launch are in already)
-                info = self._early_info(round_ok)
-                if not self._early_agg_done() and round_ok:
-                    round_ok = False
-                    info = {**self._early_agg_info, "agg_failed": True}
-                if not round_ok:
-                    self._early_launch_failed(esl, results)
+                round_ok, info = self._early_outcome(esl, results)
             else:
                 with trace.range("fl/aggregate"):
                     info = self._aggregate(U, sizes, attackers, round_ok)
@@ -992,9 +1017,8 @@ class FLEngine:
             t3 = time.perf_counter()
         self._round_meta = meta
         # ---- genuine pool for the next START (non-attacker rows stored this round; only attackers read it) ----
-        if self._has_attackers and attackers is not None and esl is None:
-            keep = [k for k in range(stored) if not bool(attackers[k])]
-            self.genuine_pool = self._take_rows(U, keep) if keep else None  # (index_select: a new tensor)
+        if self._has_attackers and U is not None and esl is None:
+            keep = self._store_genuine(U, stored)
             if (keep and keep[0] == 0 and round_ok and self.mode == "fedavg" and self.global_params is not None
                     and self.cfg.engine.get("compat-fedavg-alias", False)):
                 # A-13: the reference averages INTO the first stored update's dict, which is also the first
@@ -1008,7 +1032,7 @@ class FLEngine:
         vstream = None
         agg_done = None
         if esl is not None and self._spec is not None:
-            agg_done = esl["agg_done"]
+            agg_done = esl.agg_done
         elif self._speculative and round_ok and self.rounds_left > 1 and not last:
             if self.mode != "hyper":  # (test() falls back to the ordinary path if the model changes after this)
                 self._prefetch_validation(self.global_params)
@@ -1083,21 +1107,30 @@ class FLEngine:
             self.validation.prefetch(g)
 
     def _early_ok(self, last: bool) -> bool:
+        """Which modes launch early (``_early_launch``): FedAvg, the hypernetwork's native update, FLTrust and every
+        rule of AGGREGATORS — all device work without a host read (gmm up to 64 rows)."""
         if self.mode == "hyper":
             mode_ok = self.device.type == "cuda" and self.hyper._native_ok()
         else:
-            mode_ok = ((self.mode in ("fedavg", "FLTrust", "gmm") or self.mode in EARLY_AGGREGATORS)
+            mode_ok = ((self.mode in ("fedavg", "FLTrust") or self.mode in EARLY_AGGREGATORS)
                        and not (self.mode == "gmm" and len(self.selected) > 64) and not self.fast_fedavg
                        and self.global_params is not None
                        and not self.cfg.engine.get("compat-fedavg-alias", False))
         return self._speculative and mode_ok and self.rounds_left > 1 and not last
 
+    def _store_genuine(self, U: torch.Tensor, stored: int) -> List[int]:
+        """The genuine pool of the next START: the non-attacker rows among the first ``stored`` of ``U`` (a new
+        tensor, taken before the next START overwrites the rows).  Returns their row numbers."""
+        keep = [k for k, i in enumerate(self.selected[:stored]) if self.table[i].attack is None]
+        self.genuine_pool = self._take_rows(U, keep) if keep else None
+        return keep
+
     def _early_launch(self, st: dict, last: bool, U: Optional[torch.Tensor] = None,
-                      sel: Optional[torch.Tensor] = None) -> Optional[dict]:
-        """FedAvg on one rank with plain rows: this round's aggregate and the NEXT round's launch are enqueued
-        before the host waits for this round's training, so no host work separates two training kernels.
-        The aggregate keeps the old global model on the device when a client failed (the host learns that
-        after the wait), which makes the launch exactly this round's retry (same START, the next client
+                      sel: Optional[torch.Tensor] = None) -> Optional["EarlyLaunch"]:
+        """This round's server step and the NEXT round's launch, enqueued before the host waits for this round's
+        training (one rank, plain rows) or reads the gathered meta (several ranks), so no host work separates two
+        training kernels.  The step keeps the old global model on the device when a client failed (the host
+        learns that after the wait), which makes the launch exactly this round's retry (same START, the next client
         draws); with attackers a failure discards it and restores the host state it consumed, because their
         genuine sample then comes from the stored prefix.  Returns None where the ordinary path runs."""
         if not self._early_ok(last):
@@ -1110,117 +1143,83 @@ class FLEngine:
                 return None
             n = len(self.selected)
             U = self.local_params[:n]
-            ok_n = st["pending"].ok_device()[:n]
-            ok_all = None if self.mode == "fedavg" else (ok_n > 0).all()  # (FedAvg: decided inside the aggregate)
+            ok_all = st["pending"].ok_device()[:n]
+            if not (self.mode == "fedavg" and ok_all.dtype == torch.int32):  # (FedAvg: reduced inside the aggregate)
+                ok_all = (ok_all > 0).all()
             w = st["fedavg_w"]
             sizes = st["sizes_h"]
             attackers = torch.from_numpy(st["meta"][self._local_rows(), 3] > 0.5)
         else:  # several ranks: called on the gathered rows (device), before the host reads their meta
             P = self.P
-            ok_n = None
             ok_all = ((sel[:, P] > 0.5) & (sel[:, P + 1] > 0.5)).all()
-            s = sel[:, P + 2].double()
-            w = s / s.sum()
-            sizes = s
+            sizes = sel[:, P + 2].double()
+            w = sizes / sizes.sum()
             attackers = sel[:, P + 3] > 0.5
-        snap = ([(lc.rng.getstate(), lc.training_round, lc.genuine) for lc in self.local],
-                self.server_rng.getstate(), self.genuine_pool)
-        g_old, hyper_step, fl_old = self.global_params, None, None
-        if self.mode == "hyper":  # the update runs, or leaves the hypernetwork untouched, as the device decides
-            hyper_step = self.hyper.step
-            self.ckpt_writer.fence()  # the previous round's checkpoint copy of the arena, updated in place below
-            nxt = self._next_prep  # (staged ahead: its START models come out of the update's last launches)
-            self.hyper.train(self.selected, {i: U[k] for k, i in enumerate(self.selected)},
-                             enable=ok_all.to(torch.int32).reshape(1),
-                             gen_key=[i for _, i, _, _ in nxt["clients"]] if nxt and nxt.get("clients") else None)
-            g = g_old
-        elif self.mode == "gmm":
-            # the filter's success (some row kept) joins the clients' on the device; the host reads it after
-            # its wait from a pinned copy queued BEFORE the next launch (run_round)
-            params, ok_agg, self._early_agg_info = gmm_early(U, attackers, int(self.cfg.engine.get("gmm-rank", 1)))
-            g = torch.where(ok_all & ok_agg, params, g_old)
+        # (the next launch's host half was staged ahead: the snapshot already includes its draws, and its clients'
+        # START models come out of the hypernetwork update's last launches)
+        esl = EarlyLaunch(g_old=self.global_params, fl_old=self.fltrust_model,
+                          hyper_step=self.hyper.step if self.mode == "hyper" else None,
+                          snap=([(lc.rng.getstate(), lc.training_round, lc.genuine) for lc in self.local],
+                                self.server_rng.getstate()),
+                          prep=self._next_prep)
+        gen_key = [i for _, i, _, _ in esl.prep["clients"]] if esl.prep and esl.prep.get("clients") else None
+        esl.info, rule_ok = self._server_step(U, sizes, attackers, ok_all, w=w, gen_key=gen_key)
+        if rule_ok is not None:
+            # gmm's success (some row kept): the host reads it after its wait from a pinned copy queued BEFORE the
+            # next launch, so it waits for the filter and not for the training behind it (_early_outcome)
             okh = torch.empty(1, dtype=torch.bool, pin_memory=True)
-            okh.copy_(ok_agg.reshape(1), non_blocking=True)
+            okh.copy_(rule_ok.reshape(1), non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
-            self._early_agg_ok = (okh, ev)
-        elif self.mode == "FLTrust":
-            # the server model's training and the trust-weighted sum, all enqueued on the device (_fltrust); the
-            # server model and the trust scores are rolled back if a client failed (_early_launch_failed)
-            fl_old = self.fltrust_model
-            g = torch.where(ok_all, self._fltrust(U), g_old)
-        elif self.mode != "fedavg":
-            # a robust rule, all on the device (no host read): its result kept only when every client succeeded
-            res = AGGREGATORS[self.mode](U, sizes, attackers=None, seed=self.seed * 13 + self.round_no,
-                                        gmm_rank=int(self.cfg.engine.get("gmm-rank", 1)), **self._rule_args())
-            g = torch.where(ok_all, res.params.to(torch.float32), g_old)  # (a new tensor: never a row of U)
-            self._early_agg_info = {k: v for k, v in res.info.items() if k != "scores"}
-        else:
-            if ok_n is not None and ok_n.dtype == torch.int32 and g_old is not None:
-                g = ops.weighted_rows(U, w, ok_n, g_old)  # (the success check fused into the aggregate's pass)
-            else:
-                if ok_all is None:
-                    ok_all = (ok_n > 0).all()
-                g = torch.where(ok_all, ops.weighted_rows(U, w), g_old)
-        keep = None
-        if self._has_attackers:  # the pool of a fully stored round (before the next START overwrites U)
-            keep = [k for k, i in enumerate(self.selected) if self.table[i].attack is None]
-            self.genuine_pool = self._take_rows(U, keep) if keep else None  # (index_select: a new tensor)
-        self.global_params = g
+            esl.rule_ok = (okh, ev)
+        if self._has_attackers:  # the pool of a fully stored round
+            esl.keep = self._store_genuine(U, len(self.selected))
+            esl.pool = self.genuine_pool
         if self.mode != "hyper":
-            self._prefetch_validation(g)
-        agg_done = torch.cuda.Event()
-        agg_done.record(torch.cuda.current_stream(self.device))
-        prep = self._next_prep  # (staged ahead: the snapshot above already includes its draws)
+            self._prefetch_validation(self.global_params)
+        esl.agg_done = torch.cuda.Event()
+        esl.agg_done.record(torch.cuda.current_stream(self.device))
         self._spec = self._launch_local(self._genuine_for_attackers())
-        return {"g_old": g_old, "snap": snap, "keep": keep, "pool": self.genuine_pool, "agg_done": agg_done,
-                "prep": prep, "hyper_step": hyper_step, "fl_old": fl_old}
+        return esl
 
-    def _early_info(self, round_ok: bool) -> dict:
+    def _early_outcome(self, esl: "EarlyLaunch", results: np.ndarray):
+        """After the host's wait: (round ok, info) of a round whose server step went in early; a failed one is
+        undone (``_early_launch_failed``)."""
+        round_ok = bool(results.all())
+        info = {**esl.info, "path": "early-launch"} if round_ok else {}
+        if round_ok and esl.rule_ok is not None:
+            okh, ev = esl.rule_ok
+            ev.synchronize()
+            if not bool(okh[0]):
+                round_ok, info = False, {**esl.info, "agg_failed": True}
         if not round_ok:
-            return {}
-        if self.mode == "hyper":
-            return {"path": "early-launch", "_lazy": lambda: self.hyper.last_info}  # (as _aggregate)
-        if self.mode == "FLTrust":
-            return {"path": "early-launch"}  # (the trust scores join the record in _finish_round, as ever)
-        if self.mode != "fedavg":
-            return {**self._early_agg_info, "path": "early-launch"}
-        return {"n": len(self.selected), "path": "early-launch"}
+            self._early_launch_failed(esl, results)
+        return round_ok, info
 
-    def _early_agg_done(self) -> bool:
-        """gmm's filter success of the early launch (True for every other rule): its pinned copy was queued before
-        the next launch, so this waits for the filter only, not for the training queued behind it."""
-        ok, self._early_agg_ok = self._early_agg_ok, None
-        if ok is None:
-            return True
-        ok[1].synchronize()
-        return bool(ok[0][0])
-
-    def _early_launch_failed(self, esl: dict, results: np.ndarray) -> None:
-        self.global_params = esl["g_old"]  # (the device selected the same values: the launch's START)
-        if esl.get("fl_old") is not None:  # FLTrust: no server-model step and no trust scores for a failed round
-            self.fltrust_model = esl["fl_old"]
+    def _early_launch_failed(self, esl: "EarlyLaunch", results: np.ndarray) -> None:
+        self.global_params = esl.g_old  # (the device selected the same values: the launch's START)
+        if self.mode == "FLTrust":  # no server-model step and no trust scores for a failed round
+            self.fltrust_model = esl.fl_old
             self._trust = None
             self._fl_pending = None
-        if esl["hyper_step"] is not None:  # the device skipped the hypernetwork update: its step count too
-            self.hyper.step = esl["hyper_step"]
+        if esl.hyper_step is not None:  # the device skipped the hypernetwork update: its step count too
+            self.hyper.step = esl.hyper_step
             self.hyper._info_dev = None
-        if esl["keep"] is None:
+        if esl.keep is None:
             return  # no attackers: the launch in flight is this round's retry
         # attackers sample the stored prefix's genuine rows: discard the launch, restore what it consumed
         # (every row is stored when only the aggregate failed: gmm kept no row)
         stored = int(np.nonzero(~results)[0][0]) if not results.all() else len(results)
-        pos = [esl["keep"].index(k) for k in range(stored) if k in esl["keep"]]
-        pool = esl["pool"][pos] if pos else None
-        states, srng, _ = esl["snap"]
+        m = sum(k < stored for k in esl.keep)  # (keep ascends: the pool's first m rows)
+        states, srng = esl.snap
         for lc, (rs, tr, gen) in zip(self.local, states):
             lc.rng.setstate(rs)
             lc.training_round = tr
             lc.genuine = gen
         self.server_rng.setstate(srng)
         self._spec = None
-        self._next_prep = esl["prep"]  # the launch's host half is reused as it was (same draws)
-        self.genuine_pool = pool
+        self._next_prep = esl.prep  # the launch's host half is reused as it was (same draws)
+        self.genuine_pool = esl.pool[:m] if m else None
 
     def _client_losses(self) -> Optional[List[Optional[List[float]]]]:
         """Per-epoch training loss of every selected client (None for attackers and failed clients), from

@@ -330,6 +330,37 @@ def geomed_weights(G: torch.Tensor, alpha: torch.Tensor, iters: int = 100, nu: f
     return composite.geomed_weights(G, alpha.to(G.device), int(iters), float(nu))
 
 
+def centred_gram(U: torch.Tensor) -> torch.Tensor:
+    """n x n Gram of the rows centred on their mean (fp64).  Device, n <= 64: the fp64-MFMA Gram pass of ``agg.hip``
+    (rows centred on one of them, then double-centred) instead of a generic fp64 GEMM with M = N = n and
+    K = P (~50 k), a shape the library GEMM handles poorly."""
+    if _dev(U) and 1 <= U.shape[0] <= 64:
+        return native().gram_centred(U.to(torch.float32).contiguous())[0]
+    return composite.centred_gram(U)
+
+
+def gmm_filter(G: torch.Tensor, att: torch.Tensor, rank: int = 0):
+    """The GMM gradient filter on the centred Gram -> (keep [n] bool, info [3] fp64 = threshold, kept, ok).  Device,
+    n <= 64: ``k_gmm_filter``, one launch and no host read; host flags ``att`` go up pinned, never through a
+    pageable copy that would wait for the stream.  Otherwise its host mirror (``composite.gmm_filter_ref``)."""
+    if _dev(G) and G.shape[0] <= 64:
+        from .layers import upload
+
+        att = att.to(torch.uint8)
+        att = att if att.is_cuda else upload(att, G.device)
+        keep, info = native().gmm_filter(G.contiguous(), att.contiguous(), int(rank or 0))
+        return keep.bool(), info
+    return composite.gmm_filter(G, att, int(rank or 0))
+
+
+def top_pc(G: torch.Tensor, sweeps: int = 12) -> torch.Tensor:
+    """First principal-component scores from the centred Gram.  Device, n <= 64: a fixed-sweep Jacobi
+    eigen-decomposition (``k_top_pc``, no host read); ``torch.linalg.eigh`` on the CPU / for larger n."""
+    if _dev(G) and G.shape[0] <= 64:
+        return native().top_pc(G.contiguous(), int(sweeps))
+    return composite.top_pc(G)
+
+
 def row_norms(U: torch.Tensor) -> torch.Tensor:
     if _dev(U):
         return native().row_dots(U.contiguous(), U.new_zeros(0), 0)[:, 0].clamp_min(0).sqrt()

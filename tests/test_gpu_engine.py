@@ -200,7 +200,7 @@ def test_speculative_launch_matches_serial(gpu, tmp_path, model, attackers, mode
         hist = eng.run()
         out = (eng.hyper.hnet.arena if mode == "hyper" else eng.global_params).detach().cpu().clone()
         # (the robust rules run in the early launch too: aggregate + next launch before the host wait)
-        assert not spec or mode not in EARLY_AGGREGATORS + ("FLTrust", "gmm") or \
+        assert not spec or mode not in EARLY_AGGREGATORS + ("FLTrust",) or \
             any(r.get("path") == "early-launch" for r in hist)
         eng.close()
         return [(r["ok"], None if r["metric"] != r["metric"] else r["metric"]) for r in hist], out
@@ -244,24 +244,12 @@ def test_robust_modes_end_to_end(gpu, tmp_path, monkeypatch, mode, attack):
     def capture(U, sizes, attackers=None, seed=0, **kw):
         rows = U.detach().cpu().clone()
         res = orig_fn(U, sizes, attackers=attackers, seed=seed, **kw)
-        seen.append((rows, sizes.detach().cpu().clone(), None if attackers is None else attackers.clone(),
-                     res.params.detach().cpu().clone(), seed))
+        att = None if attackers is None else attackers.detach().cpu().clone()  # (host or device flags)
+        seen.append((rows, sizes.detach().cpu().clone(), att, res.params.detach().cpu().clone(), seed))
         return res
 
     if orig_fn is not None:
         monkeypatch.setitem(AGGREGATORS, mode, capture)
-    if mode == "gmm":  # (the early launch calls the filter without its host read)
-        import attackfl_amd.fl.engine as engine_mod
-        orig_early = engine_mod.gmm_early
-
-        def capture_early(U, attackers, gmm_rank=None):
-            rows = U.detach().cpu().clone()
-            params, ok, info = orig_early(U, attackers, gmm_rank)
-            seen.append((rows, torch.ones(U.shape[0]), attackers.detach().cpu().clone(), params.detach().cpu().clone(),
-                         eng.seed * 13 + len(seen) + 1))
-            return params, ok, info
-
-        monkeypatch.setattr(engine_mod, "gmm_early", capture_early)
     fl_seen = []
     if mode == "FLTrust":  # the rows, g_0 and the server model around every device FLTrust aggregate
         orig_fl = eng._fltrust
@@ -278,7 +266,7 @@ def test_robust_modes_end_to_end(gpu, tmp_path, monkeypatch, mode, attack):
     eng.close()
     assert [r["ok"] for r in hist] == [True, True, True]
     assert len(seen) == (0 if mode == "FLTrust" else 3)
-    if mode in EARLY_AGGREGATORS + ("FLTrust", "gmm"):
+    if mode in EARLY_AGGREGATORS + ("FLTrust",):
         assert any(r.get("path") == "early-launch" for r in hist)  # (the last round never launches early)
     if mode == "FLTrust":
         # the trust / rescale math of server.py:714-740 in fp64 on the captured rows and server delta
@@ -304,6 +292,57 @@ def test_robust_modes_end_to_end(gpu, tmp_path, monkeypatch, mode, attack):
     if mode == "FLTrust":
         assert len(hist[-1]["trust"]) == 5 and all(t >= 0.0 for t in hist[-1]["trust"])
     assert os.path.exists(os.path.join(tmp_path, "TransformerModel.pth"))
+
+
+@pytest.mark.parametrize("attackers", [False, True])
+def test_gmm_failed_filter_matches_on_both_schedules(gpu, tmp_path, monkeypatch, attackers):
+    """gmm's own failure (no row kept) on the serial path, which reads the rule's device success itself, and in the
+    early launch, which learns it from the pinned copy after the next launch is in: round 2's filter is made to
+    report failure once (only the flag is flipped), the round is retried, and both schedules give the same rounds
+    bit for bit.  With an attacker the early launch is discarded and what it consumed restored."""
+    from attackfl_amd.agg import AGGREGATORS
+
+    orig_fn = AGGREGATORS["gmm"]
+
+    def run(spec, sub):
+        state = {"eng": None, "done": False}
+
+        def fails_once(U, sizes, **kw):
+            res = orig_fn(U, sizes, **kw)
+            if state["eng"].round_no == 2 and not state["done"]:  # round 2's first attempt
+                state["done"] = True
+                res.ok = torch.zeros((), dtype=torch.bool, device=U.device)
+            return res
+
+        monkeypatch.setitem(AGGREGATORS, "gmm", fails_once)
+        d = {
+            "server": {"num-round": 4, "clients": 3, "mode": "gmm", "model": "TransformerModel", "data-name": "ICU",
+                       "data-distribution": {"num-data-range": [300, 500]}},
+            "learning": {"epoch": 2, "batch-size": 128},
+            "data": {"synthetic": True, "train-size": 4000, "test-size": 1000},
+            "engine": {"checkpoint-dir": str(tmp_path / sub), "trainer": "auto", "speculative": spec, "seed": 3},
+            "log_path": str(tmp_path / sub),
+        }
+        if attackers:
+            d["server"]["random-seed"] = 11
+        cfg = from_dict(d)
+        table = build_client_table(cfg, 1, parse_attackers("2:Min-Max:2") if attackers else None)
+        eng = state["eng"] = FLEngine(cfg, device="cuda", table=table, verbose=False)
+        assert eng._speculative == spec
+        hist = eng.run()
+        out = eng.global_params.detach().cpu().clone()
+        eng.close()
+        assert not spec or any(r.get("path") == "early-launch" for r in hist)
+        assert sum(r["ok"] for r in hist) == 4 and not any("agg_failed" in r for r in hist if r["ok"])
+        # the one extra failed round: its filter kept rows (a filter that fails by itself keeps none)
+        extra = [r for r in hist if r.get("agg_failed") and r["kept"]]
+        assert len(extra) == 1 and extra[0]["round"] == 2 and not extra[0]["ok"]
+        return [(r["ok"], None if r["metric"] != r["metric"] else r["metric"]) for r in hist], out
+
+    h0, p0 = run(False, "serial")
+    h1, p1 = run(True, "spec")
+    assert h0 == h1
+    assert torch.equal(p0, p1)
 
 
 @pytest.mark.parametrize("shape", [(6, 5000), (8, 47693), (37, 100), (3, 7), (5, 257)])
