@@ -64,24 +64,22 @@ constexpr int B_F2 = B_XIN + 4096;                 // tile16: drop(gelu(ffn.0 ou
 constexpr int B_DF0 = B_F2 + 4096;                 // tile16: d(ffn.0 pre-activation)    (dY of dWf1)
 constexpr int B_NVEC = 648;                        // 10 x 64 vectors + ffn.0 bias (8 slots, 6 real)
 constexpr int B_VEC = B_DF0 + 4096;                // fp32 [648] bias / LayerNorm parameters
-constexpr int B_CS = B_VEC + B_NVEC * 4;           // fp32 [648] their gradients (column sums)
 // The LayerNorm gradient column sums (6 x 64, produced wave-locally during the backward) are summed over
-// the 8 waves as integer quanta in fp64 LDS atomics (onchip.h lds_addq: exact) into DBL, which ALIASES CS
-// (+ 480 bytes): the remaining CS entries are written only after the backward, and the sums are moved to
-// their CS slots at the start of the update.  Integer addition makes the 8-way sum independent of the order
-// the waves arrive in by construction, so a client's trajectory is bit-reproducible whatever launch or rank
-// trains it (fp32 LDS atomics were not: ~1e-4 drift per round; fp64 ones only while the partials spanned
-// < 2^29).
+// the 8 waves as integer quanta in fp64 LDS atomics (onchip.h lds_addq: exact) into DBL; the update reads each
+// sum straight into the register of the thread that owns the entry (vec_entry), which zeroes the slot again.
+// Integer addition makes the 8-way sum independent of the order the waves arrive in by construction, so a
+// client's trajectory is bit-reproducible whatever launch or rank trains it (fp32 LDS atomics were not: ~1e-4
+// drift per round; fp64 ones only while the partials spanned < 2^29).  (The bias gradients never touch LDS: they
+// are MFMA column sums in the registers of the waves that own those entries.)
 constexpr int B_NLN = 6 * 64;
-constexpr int B_DBL = B_CS;                        // fp64 [384]: G1 B1 G2 B2 G3 B3
+constexpr int B_DBL = B_VEC + B_NVEC * 4;          // fp64 [384]: G1 B1 G2 B2 G3 B3
 constexpr int B_DBL_BYTES = B_NLN * 8;
-static_assert(B_DBL_BYTES >= B_NVEC * 4, "DBL covers CS");
 constexpr int B_MISC = B_DBL + B_DBL_BYTES;        // u32 [8] per-wave abort words, then the progress counters
 constexpr int B_CNT_A = B_MISC + 32;               // u32: waves past their out_proj backward (DO / DV stored, Wo read)
 constexpr int B_CNT_B = B_MISC + 36;               // u32: waves past their whole backward (DZ0 stored, Wv read)
 constexpr int B_CNT_C = B_MISC + 40;               // u32: waves past their ffn backward (DF3 / DF0 stored)
 constexpr int B_TOTAL = B_MISC + 64;
-// vector segments (x64 floats) of VEC / CS
+// vector segments (x64 floats) of VEC
 enum { VS_DB = 0, VS_VB, VS_OB, VS_G1, VS_B1, VS_F2B, VS_G2, VS_B2, VS_G3, VS_B3 };
 constexpr int VS_F1B = 640;  // ffn.0 bias (6 real)
 
@@ -264,16 +262,33 @@ __device__ __forceinline__ void load16(float (&x)[16], const uint32_t (&d)[8]) {
 
 // Optimizer state of one branch lane (AGPR-resident, see ar/aw; the v / out_proj blocks' weights and moments live
 // in the workspace units, see br_update):
-//  * cmp: NCMP "compact" entries, the bias / LayerNorm vectors (VEC index e < 648): entry e belongs to thread
-//    e % 512, slot e / 512.  (The dense, ffn.0 and ffn.3 weights were compact entries too, staged through LDS and
-//    updated by every thread after the staging barrier; since round 6 the leaders update them as tiles in their
-//    slack before barrier 1 — br_update, small units — and the compact pass is 2 entries per thread, not 5.)
+//  * cmp: NCMP "compact" entries, the bias / LayerNorm vectors (VEC index e < 648).  An entry belongs to the thread
+//    whose registers hold its gradient sum at the end of br_update's units (vec_entry), so the vector Adam needs
+//    no staging and no barrier: at most two entries per thread, one pass of vec_adam<2> per wave.  (The dense,
+//    ffn.0 and ffn.3 weights were compact entries too; since round 6 the leaders update them as tiles — br_update,
+//    small units.)
 constexpr int NCMP = 2;
 struct BrState {
   VS cmp[NCMP];
-  float dst[NCMP];  // AGPR: where compact entry h's new value goes (cmp_dst), fixed for the round
 };
-static_assert(B_NVEC <= NCMP * NTH, "compact entries");
+// Compact entry (VEC index, or -1) of slot h of thread (wave, lane = 16 g + i16):
+//   slot 0  waves 2-7: LayerNorm sum k = wave - 2 (DBL order), feature `lane` — the thread reads accumulator
+//           64 k + lane; wave 0, g = 0: ffn.0 bias i16 (wave 0's all-ones MFMA over the DF0 tile);
+//   slot 1  the column sums of the wave's all-ones MFMAs, one tile per lane group (every accumulator row of a
+//           column holds the same sum): g = 0, 1 the unit's dY tiles Tb, Tb + 1 (out_proj bias on waves 0, 2,
+//           in_proj.v bias on waves 4, 6), g = 2 ffn.3 bias tile w4, g = 3 dense bias tile w4 (leaders).
+__device__ __forceinline__ int vec_entry(int wave, int lane, int h) {
+  const int w4 = wave & 3, g = lane >> 4, i16 = lane & 15;
+  const bool lead = wave < 4;
+  if (h == 0) {
+    if (wave >= 2) return ln_seg(wave - 2) * 64 + lane;
+    return wave == 0 && g == 0 && VS_F1B + i16 < B_NVEC ? VS_F1B + i16 : -1;
+  }
+  if (g < 2) return (w4 & 1) == 0 ? (lead ? VS_OB : VS_VB) * 64 + 16 * (2 * (w4 >> 1) + g) + i16 : -1;
+  return lead ? (g == 2 ? VS_F2B : VS_DB) * 64 + 16 * w4 + i16 : -1;
+}
+// (the last two ffn.0 bias slots are padding)
+__device__ __forceinline__ bool vec_real(int e) { return e >= 0 && e < VS_F1B + FF; }
 
 // Every dropout keep-bit of a branch wave's forward for one step, packed into two words:
 //   mk0 = m1 (out_proj dropout, 16 bits) | m2 (ffn.3 dropout) << 16;
@@ -435,23 +450,46 @@ __device__ __forceinline__ void br_forward(uchar* smem, const float (&xin)[4], u
   }
 }
 
+// The part of the backward that does not depend on d(out): the transposed ffn.3 fragments of its first GEMM, and the
+// LayerNorm-3 input xh3 = LN(xh2 * gamma2 + beta2) with its rstd, recomputed from the saved bf16 xh2 (fewer saved registers than keeping the forward's fp32 values, and the
+// backward's own bits: the forward normalised the unrounded row).  Run by each wave while it waits for the head's
+// hand-off — gamma2 / beta2 and the image change only in the update — and held in registers (25) across the wait.
+// (Holding gamma3 too measured inside the noise, gamma2 as well spilled: profiles/ab_tf2_tail.log.)
+struct BwdPre {
+  float xh3[16], rstd3;
+  s8v f3[2];  // the transposed ffn.3 image fragments of the backward's first GEMM (final since the last update)
+};
+__device__ __forceinline__ void br_bwd_pre(const uchar* smem, const Saved& sv, BwdPre& bp, int lane) {
+  const uchar* vg = lane_vec(smem + B_VEC, lane >> 4);
+  float gm[16], bt[16];
+  load16(bp.xh3, sv.xh2);
+  vec16g(gm, vg + VS_G2 * 256);
+  vec16g(bt, vg + VS_B2 * 256);
+  affine2(bp.xh3, bp.xh3, gm, bt);
+  bp.rstd3 = ln_fwd2(bp.xh3);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) asm volatile("" : "+v"(bp.xh3[j]));  // (computed here, not sunk below the wait)
+  asm volatile("" : "+v"(bp.rstd3));
+  bp.f3[0] = wtfrag<true>(smem + B_IMG_F2, LD32, 0, 0, lane);
+  bp.f3[1] = wtfrag<true>(smem + B_IMG_F2, LD32, 0, 1, lane);
+  asm volatile("" : "+v"(bp.f3[0]), "+v"(bp.f3[1]));
+}
+
 // d(branch output) -> every activation gradient of the branch (wave-local), the dY tiles of the dW
 // GEMMs and the column sums of the vector gradients
 template <int BR>
-__device__ __forceinline__ void br_backward(uchar* smem, const float (&dout)[16], const Saved& sv, const AdamK& K, int lane,
-                                            int wave) {
+__device__ __forceinline__ void br_backward(uchar* smem, const float (&dout)[16], const Saved& sv, const BwdPre& bp,
+                                            const AdamK& K, int lane, int wave) {
   opq(lane, wave);
   const int g = lane >> 4, r = 16 * wave + (lane & 15);
   const uchar* vg = lane_vec(smem + B_VEC, g);
   float dr2[16];
   sb();
-  {  // LayerNorm 3 and 2 backward (xh3 = LN(xh2 * gamma2 + beta2) recomputed: fewer saved registers)
-    float gm[16], t[16], dx[16], xh[16], bt[16];
-    load16(xh, sv.xh2);
-    vec16g(gm, vg + VS_G2 * 256);
-    vec16g(bt, vg + VS_B2 * 256);
-    affine2(xh, xh, gm, bt);
-    const float rstd3 = ln_fwd2(xh);
+  {  // LayerNorm 3 and 2 backward (xh3 and rstd3 from br_bwd_pre)
+    float gm[16], t[16], dx[16], xh[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) xh[j] = bp.xh3[j];
+    const float rstd3 = bp.rstd3;
 #pragma unroll
     for (int j = 0; j < 16; ++j) t[j] = dout[j] * xh[j];
     if (!ABL(K, ABL_COLSUM)) ln_colsum(smem, 4, t, lane);
@@ -474,8 +512,8 @@ __device__ __forceinline__ void br_backward(uchar* smem, const float (&dout)[16]
     for (int j = 0; j < 16; ++j) d3[j] = keepf(dr2[j] * INV_K01, sv.m2, j);
 #pragma unroll
     for (int t = 0; t < 4; ++t) st4<TK64>(smem + B_DF3, r, 4 * t + g, d3 + 4 * t);
-    f4v acc = mma(wtfrag<true>(smem + B_IMG_F2, LD32, 0, 0, lane), bfrag(d3, 0), Z4);
-    acc = mma(wtfrag<true>(smem + B_IMG_F2, LD32, 0, 1, lane), bfrag(d3, 1), acc);
+    f4v acc = mma(bp.f3[0], bfrag(d3, 0), Z4);
+    acc = mma(bp.f3[1], bfrag(d3, 1), acc);
 #pragma unroll
     for (int i = 0; i < 4; ++i) df0[i] = acc[i] * sv.gk[i];
     st4<TK16>(smem + B_DF0, r, g, df0);
@@ -544,14 +582,7 @@ __device__ __forceinline__ void br_backward(uchar* smem, const float (&dout)[16]
 // compact entry e (< 648: a bias / LayerNorm vector element) of branch BR: flat parameter index (or -1)
 template <int BR>
 __device__ __forceinline__ int cmp_param(int e) {
-  return e < B_NVEC ? BrK<BR>::vec_param(e) : -1;
-}
-// store descriptor of compact entry e for U3 (fp32 store into VEC); padding entries and entries past the end point
-// at this lane's dummy word (DF0 tile) instead
-template <int BR>
-__device__ __forceinline__ uint32_t cmp_dst(int e, int lane) {
-  const uint32_t dmy = B_DF0 + 768 + 4 * lane;
-  return cmp_param<BR>(e) >= 0 ? (0x80000000u | (uint32_t)(B_VEC + 4 * e)) : (0x80000000u | dmy);
+  return vec_real(e) ? BrK<BR>::vec_param(e) : -1;
 }
 
 // ------------------------------------------------------------------------------ branch weight update
@@ -717,6 +748,37 @@ __device__ __forceinline__ void smu_img(uchar* smem, const f4v (&S)[9], int w4, 
   }
 }
 
+// Adam on a thread's vector entries in the stages of adam_staged (onchip.h), with every contraction written out:
+//   m' = fma(c1, g - keep m, keep m);  v' = fma(g, (1 - b2) g, b2 v);
+//   p' = fma(-(lr_bc1 m'), 1 / fma(rsqrt_bc2, sqrt(v'), eps), p).
+// Which products of `b2 v + (1 - b2) g g` the compiler fuses depends on the code around the call (the gradient as a
+// register select instead of an LDS read moved the fused product and the low bit of v'); a trained model must not
+// change with that, so this pass pins the form it has always compiled to.
+template <int N>
+__device__ __forceinline__ void vec_adam(VS (&pa)[N], float (&m)[N], float (&v)[N], const float (&g)[N], float (&pn)[N],
+                                         const AdamK& K) {
+#pragma clang fp contract(off)
+  float den[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    pn[i] = ar(pa[i].p);
+    const float mk = m[i] * K.keep;
+    m[i] = __builtin_fmaf(K.c1, g[i] - mk, mk);
+    const float t = (1.f - fk::B2) * g[i], u = fk::B2 * v[i];
+    v[i] = __builtin_fmaf(g[i], t, u);
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) den[i] = __builtin_amdgcn_sqrtf(v[i]);
+#pragma unroll
+  for (int i = 0; i < N; ++i) den[i] = __builtin_amdgcn_rcpf(__builtin_fmaf(K.rsqrt_bc2, den[i], K.eps));
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const float lm = K.lr_bc1 * m[i];
+    pn[i] = __builtin_fmaf(-lm, den[i], pn[i]);
+    pa[i].p = aw(pn[i]);
+  }
+}
+
 // Weight gradients + Adam for one step, started by each wave as soon as its own backward is done — no barrier
 // between the backward and the weight-gradient work.  The waves of a SIMD pair run the same chain and the arbiter
 // favours the older one, so waves 0-3 ("leaders") reach this point ~2.5 us before waves 4-7 ("laggards", the
@@ -731,12 +793,15 @@ __device__ __forceinline__ void smu_img(uchar* smem, const f4v (&S)[9], int w4, 
 //   laggards  counter A (the v unit's dY rows): their in_proj.v unit, whose new bf16 weights wait for counter B (the
 //             v image is read until the end of every wave's backward).
 // The leaders then run Adam on their small unit (the dense / ffn.3 / ffn.0 tiles, workspace-resident like the
-// blocks) and write its images — in their slack while the laggards finish the v block.  The bias sums are held in
-// registers until barrier 1; then they and the LayerNorm sums (fixed-point accumulators DBL, aliasing CS) are
-// stored; barrier 2; every thread runs Adam on its compact entries (U3: the 648 bias / LayerNorm elements, 2 per
-// thread — 5 when the small weights were compact entries too: +3.6 %, profiles/ab_tf2_r6_update.log).  The abort decision
-// (a NaN loss anywhere in the batch) is taken by every wave after counter A or B — every abort word is written
-// before its wave signals — before anything is updated.  Returns false on abort.
+// blocks) and write its images — in their slack while the laggards finish the v block.  Last, every wave runs Adam
+// on the vector entries it owns (the 648 bias / LayerNorm elements, at most 2 per thread): an entry belongs to the
+// thread whose registers hold its gradient sum — a column of one of the wave's all-ones MFMA accumulators, or the
+// LayerNorm accumulator the thread reads (vec_entry) — so nothing is staged through LDS and the only barrier after
+// the units is the step's end barrier.  (Before, the sums went to an fp32 staging array behind one barrier and
+// were read back by thread e % 512 behind a second: 0.8 us of every wave's step; and 5 entries per thread when the
+// small weights were vector entries too: +3.6 %, profiles/ab_tf2_r6_update.log.)  The abort decision (a NaN loss
+// anywhere in the batch) is taken by every wave after counter A — every abort word is written before its wave
+// signals — before anything is updated.  Returns false on abort.
 // (Measured first: the leaders taking both units after counter A was 1 % slower — A is reached only ~0.2 us
 // before B, so the leaders' two units became the tail; profiles/ab_tf2_r6_update.log.)
 template <int BR>
@@ -745,13 +810,14 @@ __device__ __forceinline__ bool br_update(uchar* smem, BrState& st, const AdamK&
   using B = BrK<BR>;
   opq(lane, wave);
   asm volatile("" : "+v"(tid));
-  const int w4 = wave & 3, g = lane >> 4, i16 = lane & 15;
+  const int w4 = wave & 3, g = lane >> 4;
   const bool lead = wave < 4;
   const uint32_t all = 8u * (uint32_t)step;
   LDS_AS uint32_t* abort_w = ldsu(smem, B_MISC);
   const int Ta = 2 * (w4 & 1), Tb = 2 * (w4 >> 1);
   const bool do_bias = (w4 & 1) == 0;  // one of the two units that read dY tiles Tb, Tb + 1
-  f4v bsu[2];                          // the unit's bias sums (out_proj on leaders, v on laggards)
+  f4v bsu[2] = {Z4, Z4};               // the unit's bias sums (out_proj on leaders, v on laggards)
+  f4v cmom;                            // the compact entries' moments m0 m1 v0 v1
   f4v as = Z4, bd = Z4, a3 = Z4, af1 = Z4, b3 = Z4, b1 = Z4;  // leaders: dense / ffn.3 / ffn.0 tiles + bias sums
   const int ui = 2 * w4 + (lead ? 0 : 1);
   f4v U[12];
@@ -803,6 +869,7 @@ __device__ __forceinline__ bool br_update(uchar* smem, BrState& st, const AdamK&
     if (!ABL(K, ABL_UADAM)) unit_adam(U, acc, K);
     u32x2v w[4];
     unit_pack(U, w);
+    cmom = mom_ld(rm, 0, tid);  // (issued here: in flight over the wait for B, the image and the unit's stores)
     if (!lead && !lds_wait(smem, B_CNT_B, all)) {  // (the v image is read until the end of every wave's backward)
       if (lane == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       return false;
@@ -833,55 +900,30 @@ __device__ __forceinline__ bool br_update(uchar* smem, BrState& st, const AdamK&
 #pragma unroll
     for (int j = 0; j < 9; ++j) smu_st(rm, w4, j, lane, S[j]);
   }
-  // LayerNorm gradient sums out of the fp64 accumulators (complete: counter B; DBL aliases CS, written back below)
-  const float lnsum = tid < B_NLN ? lds_getq(smem + B_DBL, tid) : 0.f;
-  const f4v cmom = mom_ld(rm, 0, tid);  // compact entries' m0 m1 v0 v1
+  // ---- the vector entries (648 bias / LayerNorm elements), owner-computed: every gradient sum is already in a
+  // register of the thread that owns the entry (vec_entry) — the bias sums in the all-ones MFMA accumulators, the
+  // LayerNorm sums read here from the fp64 accumulators (complete at counter B, which every wave has passed) — so
+  // Adam runs on them at once and each owner writes its VEC words itself.  No staging, no barrier: VEC is read
+  // again only by the next forward, after the end barrier; the accumulator slot is zeroed by its reader and
+  // added to again only after that barrier.  Threads without an entry compute on zeros and store nothing.
   stp(5, tid);
   prio_hi();
-  lds_bar();
-  {
-    LDS_AS float* cs = ldsf(smem, B_CS);
-    if (tid < B_NLN) cs[ln_seg(tid >> 6) * 64 + (tid & 63)] = lnsum;
-    if (do_bias && g == 0) {
-#pragma unroll
-      for (int b = 0; b < 2; ++b) cs[(lead ? VS_OB : VS_VB) * 64 + 16 * (Tb + b) + i16] = bsu[b][0];
-    }
-    if (lead) {
-      if (g == 0) {
-        cs[VS_F2B * 64 + 16 * w4 + i16] = b3[0];
-        cs[VS_DB * 64 + 16 * w4 + i16] = bd[0];
-        if (wave == 0 && i16 < FF) cs[VS_F1B + i16] = b1[0];
-      }
-    }
+  float gr[NCMP];
+  gr[0] = b1[0];
+  if (wave >= 2) {
+    LDS_AS double* q = (LDS_AS double*)(smem + B_DBL) + 64 * (wave - 2) + lane;
+    gr[0] = lds_getq(smem + B_DBL, 64 * (wave - 2) + lane);
+    *q = 0.0;
   }
-  lds_bar();
-  stp(6, tid);
-  // ---- U3: compact entries, branch-free: every entry reads its gradient (CS or GS), runs Adam and
-  // makes three stores whose addresses come from its precomputed descriptor (cmp_dst): the real ones
-  // land in VEC / CS (fp32) or a weight image (bf16), the others in per-lane dummy words of the DF0 tile
-  // (dead until the next backward).  Entries past the end or padding compute on garbage that only
-  // reaches the dummies.  (The divergent if / else version was ~1,200 instructions, 1.4 us per step.)
-  if (tid < (B_DBL_BYTES - B_NVEC * 4) / 4) ldsf(smem, B_CS)[B_NVEC + tid] = 0.f;
+  gr[1] = g == 0 ? bsu[0][0] : g == 1 ? bsu[1][0] : g == 2 ? b3[0] : bd[0];
   float mm[NCMP] = {cmom[0], cmom[1]}, vv[NCMP] = {cmom[2], cmom[3]};
   if (!ABL(K, ABL_U3)) {
-    const int dmy = B_DF0 + 4 * (tid & 63);
-    float gr[NCMP], pn[NCMP];
+    float pn[NCMP];
+    vec_adam<NCMP>(st.cmp, mm, vv, gr, pn, K);
 #pragma unroll
     for (int h = 0; h < NCMP; ++h) {
-      const int e = tid + NTH * h;
-      gr[h] = e < B_NVEC ? *(const LDS_AS float*)(smem + B_CS + 4 * e) : 0.f;  // (past the end: dummies only)
-    }
-    adam_staged<NCMP>(st.cmp, mm, vv, gr, pn, K);
-#pragma unroll
-    for (int h = 0; h < NCMP; ++h) {
-      const int e = tid + NTH * h;
-      const uint32_t d = aru(st.dst[h]);
-      const bool vec = e < B_NVEC;
-      const bool f32 = d >> 31;
-      const int off = (int)(d & 0x7FFFFFFFu);
-      *(LDS_AS float*)(smem + (vec ? B_CS + 4 * e : dmy)) = 0.f;
-      *(LDS_AS float*)(smem + (f32 ? off : dmy + 256)) = pn[h];
-      *(LDS_AS unsigned short*)(smem + (f32 ? dmy + 512 : off)) = fk::f2bf(pn[h]);
+      const int e = vec_entry(wave, lane, h);  // (a few VALU per step: as AGPR state the two offsets spilled)
+      if (vec_real(e)) ldsf(smem, B_VEC)[e] = pn[h];
     }
   }
   mom_st(rm, 0, tid, f4v{mm[0], mm[1], vv[0], vv[1]});
@@ -933,16 +975,14 @@ __device__ __forceinline__ void br_init(uchar* smem, BrState& st, const float* P
   }
 #pragma unroll
   for (int h = 0; h < NCMP; ++h) {
-    const int e = tid + NTH * h;
+    const int e = vec_entry(wave, lane, h);
     float p0 = 0.f;
-    if (e < B_NVEC) {
+    if (e >= 0) {
       const int pi = cmp_param<BR>(e);
       p0 = pi >= 0 ? P[pi] : 0.f;
       ldsf(smem, B_VEC)[e] = p0;
-      ldsf(smem, B_CS)[e] = 0.f;
     }
     st.cmp[h] = VS{aw(p0)};
-    st.dst[h] = awu(cmp_dst<BR>(e, lane));
   }
 }
 
@@ -950,6 +990,7 @@ template <int BR>
 __device__ __forceinline__ void br_fini(const BrState& st, float* P, __amdgpu_buffer_rsrc_t rm, int lane, int wave,
                                         int tid) {
   using B = BrK<BR>;
+  opq(lane, wave);  // (addresses recomputed here, not carried from br_init across the step loop)
   {  // the units' weights (stored by the waves that updated them: wait for every store before reading back)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -981,8 +1022,8 @@ __device__ __forceinline__ void br_fini(const BrState& st, float* P, __amdgpu_bu
   }
 #pragma unroll
   for (int h = 0; h < NCMP; ++h) {
-    const int e = tid + NTH * h;
-    if (e < B_NVEC) {
+    const int e = vec_entry(wave, lane, h);
+    if (e >= 0) {
       const int pi = cmp_param<BR>(e);
       if (pi >= 0) P[pi] = ar(st.cmp[h].p);
     }
@@ -1079,6 +1120,10 @@ __device__ __forceinline__ void branch_main(const AflTfTrainArgs& a, int cid, uc
       mka0 = awu(m0);
       mka1 = awu(m1);
     }
+    BwdPre bp;  // (while the head works too: the backward then starts on d(out) at once)
+    sb();
+    br_bwd_pre(smem, sv, bp, lane);
+    sb();
     stp(1, tid);
     u32x4 du[2];
     const int go[1] = {gr_off(1, BR, wave, lane)};
@@ -1087,6 +1132,7 @@ __device__ __forceinline__ void branch_main(const AflTfTrainArgs& a, int cid, uc
     stp(2, tid);
     if (fv == 0xFFFFFFFFu) {  // timed out: abort the step for every wave (they wait on this wave's progress)
       if (lane == 0) abort_w[wave] = 1u;
+      lds_signal(smem, B_CNT_C, lane);
       lds_signal(smem, B_CNT_A, lane);
       lds_signal(smem, B_CNT_B, lane);
       failed = true;
@@ -1097,11 +1143,12 @@ __device__ __forceinline__ void branch_main(const AflTfTrainArgs& a, int cid, uc
     if (lane == 0) abort_w[wave] = fv & 1u;
 #ifndef TF2_NO_BWD
     asm volatile(";MARK bwd");
-    br_backward<BR>(smem, dout, sv, K, lane, wave);
+    br_backward<BR>(smem, dout, sv, bp, K, lane, wave);
     asm volatile(";MARK bwd_end");
     stp(3, tid);
 #else
     for (int j = 0; j < 16; ++j) asm volatile("" :: "v"(dout[j]));
+    lds_signal(smem, B_CNT_C, lane);
     lds_signal(smem, B_CNT_A, lane);
     lds_signal(smem, B_CNT_B, lane);
 #endif
