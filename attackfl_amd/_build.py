@@ -81,8 +81,9 @@ def build(verbose: bool = False, jobs: int = 0) -> str:
     host_flags = common + ["-DTORCH_EXTENSION_NAME=_C", "-DTORCH_API_INCLUDE_EXTENSION_H", "-DUSE_ROCM",
                            "-I" + py_inc, "-I" + os.path.join(ROCM, "include")] + ["-I" + p for p in inc] + ["-x", "c++"]
     kernels = sorted(glob.glob(os.path.join(ROOT, "csrc", "kernels", "*.hip")))
-    # per-file device flags: the on-chip trainers (tf2 / rnn2) keep their optimizer state in AGPRs, so its MFMAs must accumulate
-    # in VGPRs (otherwise their accumulators compete with that state for the AGPR half of the budget)
+    # per-file device flags: the on-chip trainers' MFMAs accumulate in VGPRs.  rnn2 keeps its optimizer state in AGPRs
+    # (otherwise the accumulators compete with that state for the AGPR half of the budget); tf2 uses no AGPRs at all
+    # (onchip.h ONCHIP_NO_AGPR), and an AGPR-form MFMA would bring the 128 + 128 split back
     extra = {f: ["-mllvm", "-amdgpu-mfma-vgpr-form"] for f in ("tf2.hip", "tf2_stamps.hip", "rnn2.hip", "rnn2_stamps.hip")}
     if os.environ.get("AFL_DEV_DEFINES"):  # A/B variant builds (tools/ab_native.sh): extra -D flags on every kernel
         dev_flags = dev_flags + os.environ["AFL_DEV_DEFINES"].split()

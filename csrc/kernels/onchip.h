@@ -323,13 +323,12 @@ __device__ __forceinline__ void affine2(float (&y)[16], const float (&x)[16], co
 }
 
 // ------------------------------------------------------------------------------------------- Adam
-// fp32 master weights live in ACCUMULATION registers (AGPRs) for the whole round: every access goes
-// through v_accvgpr_read / v_accvgpr_write, so the register allocator gives them the AGPR class and the
-// forward / backward working set keeps the architectural VGPRs (the two files share one 256-entry budget
-// per lane at two waves per SIMD).  Their Adam moments m, v do NOT fit beside them: with p, m and v all in
-// AGPRs the allocator spilled ~50 dwords of state to scratch, reloaded one dependent load at a time (~8 us
-// of a 29 us step).  The moments therefore live in the workspace slab (WS_MOM) and every update phase
-// issues all of its moment loads as one batch before the work that precedes the Adam arithmetic.
+// The state a lane keeps for the whole round (rnn2.hip: its W_ih tiles and compact entries; tf2.hip: the head's fc
+// tiles and at most two bias / LayerNorm entries per branch lane, the next step's dropout masks) is read and written
+// through ar / aw below.  Its Adam moments m, v do NOT fit beside it: with p, m and v all in registers the allocator
+// spilled ~50 dwords of state to scratch, reloaded one dependent load at a time (~8 us of a 29 us step).  The moments
+// therefore live in the workspace slab (WS_MOM) and every update phase issues all of its moment loads as one batch
+// before the work that precedes the Adam arithmetic.
 struct TS {  // one 16x16 weight-gradient tile's 4 elements of this lane
   float p[4];
 };
@@ -367,6 +366,18 @@ __device__ __forceinline__ void slot_st(__amdgpu_buffer_rsrc_t rs, int s, int ti
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, tid16, s * NTH * 16, 0);
   store_guard();
 }
+// ar / aw: the register class of that state, chosen per including file (define ONCHIP_NO_AGPR before the include).
+//  * default (rnn2.hip): ACCUMULATION registers.  Every access is a v_accvgpr_read / v_accvgpr_write, so the
+//    allocator gives the state the AGPR class and the forward / backward working set keeps the 128 architectural
+//    VGPRs; at two waves per SIMD the two files share one 256-entry budget per lane.  Right where the parked state is
+//    large (rnn2's W_ih tiles fill the AGPR half).
+//  * ONCHIP_NO_AGPR (tf2.hip): one class.  A function that may need AGPRs has its budget halved into 128 + 128, and
+//    once the parked state is small (tf2 after round 6: ~4 registers per branch lane, ~21 per head lane) the AGPR half
+//    is mostly the allocator's overflow for a working set that does not fit in 128, paid for with v_accvgpr copies on
+//    a VALU-issue-bound chain (tf2: 99 of 728 VALU instructions in the forward, 92 of 961 in the backward;
+//    profiles/isa_counts_tf2_regs.md).  Here the accessors are opaque identities on a "+v" operand: the optimiser sees
+//    the data flow of the asm form (nothing is contracted or reassociated across the former boundary, results bit
+//    for bit the same), nothing is issued, and the allocator has 256 VGPRs.
 #ifndef ONCHIP_NO_AGPR
 __device__ __forceinline__ float ar(float a) {
   float r;
@@ -378,9 +389,15 @@ __device__ __forceinline__ float aw(float v) {
   asm("v_accvgpr_write_b32 %0, %1" : "=a"(r) : "v"(v));
   return r;
 }
-#else  // state in architectural VGPRs (the allocator then has the whole 256-register budget for one class)
-__device__ __forceinline__ float ar(float a) { return a; }
-__device__ __forceinline__ float aw(float v) { return v; }
+#else  // one class: opaque identities (the optimiser sees the data flow of the asm above, with no copy to issue)
+__device__ __forceinline__ float ar(float a) {
+  asm("" : "+v"(a));
+  return a;
+}
+__device__ __forceinline__ float aw(float v) {
+  asm("" : "+v"(v));
+  return v;
+}
 #endif
 // Step constants.  Adam (torch.optim.Adam defaults): keep = 1, c1 = 1 - beta1, lr_bc1 = lr / (1 - beta1^t),
 // rsqrt_bc2 = 1 / sqrt(1 - beta2^t), eps = 1e-8.  SGD test mode (raw gradients for the tests): keep = 0,
@@ -396,7 +413,7 @@ __device__ __forceinline__ AdamK adam_k(const AflTfTrainArgs& a, int step) {
   const float* k = a.kt + 2 * (step - 1);
   return AdamK{k[0], k[1], 1.f, 1.f - fk::B1, fk::EPS};
 }
-// one Adam step of an AGPR-resident weight with its moments m, v (VGPRs, updated in place); v_sqrt_f32
+// one Adam step of a register-resident weight (ar / aw) with its moments m, v (updated in place); v_sqrt_f32
 // (1 ulp) instead of the correctly rounded sqrt expansion: 4x fewer instructions on the update's chain
 __device__ __forceinline__ float adam1(float& pa, float& m, float& v, float g, const AdamK& k) {
   float p = ar(pa);

@@ -6,9 +6,10 @@
 // What differs from transformer.hip: after the prologue NOTHING of a client's model lives in global
 // memory.  Per workgroup:
 //   * the head's fp32 master weights and the branches' compact entries (biases, LayerNorm, the small dense /
-//     ffn weights) stay in REGISTERS (AGPRs) for the whole round; their Adam moments, and the branches'
-//     64 x 64 v / out_proj blocks (weights AND moments), sit in a per-workgroup workspace slab that each
-//     update phase loads ahead of its arithmetic (L2-resident; see br_update for why the blocks moved there);
+//     ffn weights) stay in REGISTERS for the whole round (one class, no AGPRs: onchip.h ar / aw); their Adam
+//     moments, and the branches' 64 x 64 v / out_proj blocks (weights AND moments), sit in a per-workgroup
+//     workspace slab that each update phase loads ahead of its arithmetic (L2-resident; see br_update for why the
+//     blocks moved there);
 //   * bf16 weight images (the MFMA operands) and an fp32 copy of the bias / LayerNorm vectors live in
 //     LDS; Adam rewrites them in place;
 //   * activations chain in registers: every GEMM is computed transposed, Y^T = W . X^T, so the
@@ -32,6 +33,7 @@
 #include "kernels.h"
 #include "tf_common.h"
 #include "fused_common.h"
+#define ONCHIP_NO_AGPR  // one register class for this file's kernels (onchip.h ar / aw)
 #include "onchip.h"
 
 using namespace tf;
@@ -260,7 +262,7 @@ __device__ __forceinline__ void load16(float (&x)[16], const uint32_t (&d)[8]) {
   }
 }
 
-// Optimizer state of one branch lane (AGPR-resident, see ar/aw; the v / out_proj blocks' weights and moments live
+// Optimizer state of one branch lane (register-resident, see ar/aw; the v / out_proj blocks' weights and moments live
 // in the workspace units, see br_update):
 //  * cmp: NCMP "compact" entries, the bias / LayerNorm vectors (VEC index e < 648).  An entry belongs to the thread
 //    whose registers hold its gradient sum at the end of br_update's units (vec_entry), so the vector Adam needs
@@ -294,7 +296,7 @@ __device__ __forceinline__ bool vec_real(int e) { return e >= 0 && e < VS_F1B + 
 //   mk0 = m1 (out_proj dropout, 16 bits) | m2 (ffn.3 dropout) << 16;
 //   mk1 = matt (attention dropout per head, 4 bits) | kf (ffn.0 dropout of features 4g + i) << 4.
 // The branch computes the NEXT step's masks while it waits for the head (the wave is idle there) and
-// parks them in two AGPRs, so the ~20 hashes per lane leave the forward's critical path.
+// parks them in two registers, so the ~20 hashes per lane leave the forward's critical path.
 template <int BR>
 __device__ __forceinline__ void br_masks(uint32_t key, int r, int g, uint32_t& mk0, uint32_t& mk1) {
   const uint32_t ha = hash3(key, 8 * BR + L_ATT, r, 0), hb = hash3(key, 8 * BR + L_ATT, r, 1);
@@ -454,7 +456,8 @@ __device__ __forceinline__ void br_forward(uchar* smem, const float (&xin)[4], u
 // LayerNorm-3 input xh3 = LN(xh2 * gamma2 + beta2) with its rstd, recomputed from the saved bf16 xh2 (fewer saved registers than keeping the forward's fp32 values, and the
 // backward's own bits: the forward normalised the unrounded row).  Run by each wave while it waits for the head's
 // hand-off — gamma2 / beta2 and the image change only in the update — and held in registers (25) across the wait.
-// (Holding gamma3 too measured inside the noise, gamma2 as well spilled: profiles/ab_tf2_tail.log.)
+// (Holding gamma3 too measured inside the noise, gamma2 as well spilled: profiles/ab_tf2_tail.log; in one register
+// class gamma3 alone spills the hand-off store offsets and measured -2.8 %: profiles/ab_tf2_regs.log.)
 struct BwdPre {
   float xh3[16], rstd3;
   s8v f3[2];  // the transposed ffn.3 image fragments of the backward's first GEMM (final since the last update)
@@ -922,7 +925,9 @@ __device__ __forceinline__ bool br_update(uchar* smem, BrState& st, const AdamK&
     vec_adam<NCMP>(st.cmp, mm, vv, gr, pn, K);
 #pragma unroll
     for (int h = 0; h < NCMP; ++h) {
-      const int e = vec_entry(wave, lane, h);  // (a few VALU per step: as AGPR state the two offsets spilled)
+      // (a few VALU per step: kept as per-thread state the two offsets spill, in two register classes and in one:
+      // profiles/ab_tf2_tail.log, profiles/ab_tf2_regs.log)
+      const int e = vec_entry(wave, lane, h);
       if (vec_real(e)) ldsf(smem, B_VEC)[e] = pn[h];
     }
   }
@@ -1030,9 +1035,16 @@ __device__ __forceinline__ void br_fini(const BrState& st, float* P, __amdgpu_bu
   }
 }
 
-// this lane's 4 input features (4g + i) of row r of the batch starting at b0 of epoch e
+// this lane's 4 input features (4g + i) of row r = 16 wave + (lane & 15) of the batch starting at b0 of epoch e
 template <int BR>
-__device__ __forceinline__ void load_x(float (&x)[4], const AflTfTrainArgs& a, int cid, const Walk& w, int r, int g) {
+__device__ __forceinline__ void load_x(float (&x)[4], const AflTfTrainArgs& a, int cid, const Walk& w, int lane,
+                                       int wave) {
+  // (lane / wave opaque: the row index and the 64-bit column term of the row address are rebuilt here, in the hand-off
+  // window where the wave only waits, instead of being held across the step — as loop-invariant state they were the
+  // values the one-class allocation spilled to scratch and reloaded inside the step loop)
+  asm volatile("" : "+v"(lane));
+  asm volatile("" : "+s"(wave));
+  const int r = 16 * (wave & 7) + (lane & 15), g = (lane & 63) >> 4;
   const int Bn = min(a.batch, a.nd[cid] - w.b0);
   const gi32* ord = (const gi32*)(a.order + ((long)cid * a.E + w.e) * a.maxnd);
   const bool valid = r < Bn;
@@ -1048,7 +1060,7 @@ __device__ __forceinline__ void load_x(float (&x)[4], const AflTfTrainArgs& a, i
 __device__ __forceinline__ void stamp_init(Stamp& stp, const AflTfTrainArgs& a, uchar* smem) {
 #ifdef TF2_STAMPS
   stp.on = a.stamps && (long)blockIdx.x == (long)a.stamps[63];
-  stp.who = a.stamps ? 64 * (int)(a.stamps[62] & 7) : 0;
+  stp.who = __builtin_amdgcn_readfirstlane(a.stamps ? 64 * (int)(a.stamps[62] & 7) : 0);  // (an SGPR, not a held VGPR)
   stp.smem = smem;
   if (threadIdx.x == 0) *(LDS_AS uint64_t*)(smem + ST_OFF + 8 * (ST_N - 1)) = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1087,8 +1099,8 @@ __device__ __forceinline__ void branch_main(const AflTfTrainArgs& a, int cid, uc
   Walk w{0, 0};
   float xin[4];
   bool more = walk_valid(w, nd, BS, E);
-  if (more) load_x<BR>(xin, a, cid, w, 16 * wave + (lane & 15), g);
-  float mka0, mka1;  // the next forward's dropout masks (br_masks), parked in AGPRs
+  if (more) load_x<BR>(xin, a, cid, w, lane, wave);
+  float mka0, mka1;  // the next forward's dropout masks (br_masks), parked through awu / aru
   {
     uint32_t m0, m1;
     br_masks<BR>(afl_hash32(seed, 1u), 16 * wave + (lane & 15), g, m0, m1);
@@ -1113,7 +1125,7 @@ __device__ __forceinline__ void branch_main(const AflTfTrainArgs& a, int cid, uc
     prio_lo();
     w.b0 += BS;  // prefetch the next batch's inputs while the head works
     more = walk_valid(w, nd, BS, E);
-    if (more) load_x<BR>(xin, a, cid, w, 16 * wave + (lane & 15), g);
+    if (more) load_x<BR>(xin, a, cid, w, lane, wave);
     {  // the next step's dropout masks, while the head works (this wave would only spin)
       uint32_t m0, m1;
       br_masks<BR>(afl_hash32(seed, (uint32_t)(step + 1)), 16 * wave + (lane & 15), g, m0, m1);
@@ -1443,35 +1455,43 @@ __device__ __forceinline__ void head_main(const AflTfTrainArgs& a, int cid, ucha
     stp(12, tid);
     // ---- weight gradients + Adam
     {
-      const int Ta = 2 * (wave & 3), Tb = 2 * (wave >> 2);
+      int ln = lane, wv = wave;
+      opq(ln, wv);  // (the phase's tile addresses recomputed here, not held across the step)
+      const int Ta = 2 * (wv & 3), Tb = 2 * (wv >> 2);
       f4v acc[2][2] = {{Z4, Z4}, {Z4, Z4}};
       f4v a2 = Z4;
-      const int T2 = wave & 3, Tn2 = wave >> 2;
+      const int T2 = wv & 3, Tn2 = wv >> 2;
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        const s8v x0 = tfrag<TK128>(smem + H_CAT, 32 * s, Ta, lane), x1 = tfrag<TK128>(smem + H_CAT, 32 * s, Ta + 1, lane);
-        const s8v y0 = tfrag<TK64>(smem + H_DZ1, 32 * s, Tb, lane), y1 = tfrag<TK64>(smem + H_DZ1, 32 * s, Tb + 1, lane);
+        const s8v x0 = tfrag<TK128>(smem + H_CAT, 32 * s, Ta, ln), x1 = tfrag<TK128>(smem + H_CAT, 32 * s, Ta + 1, ln);
+        const s8v y0 = tfrag<TK64>(smem + H_DZ1, 32 * s, Tb, ln), y1 = tfrag<TK64>(smem + H_DZ1, 32 * s, Tb + 1, ln);
         acc[0][0] = mma(x0, y0, acc[0][0]);
         acc[0][1] = mma(x0, y1, acc[0][1]);
         acc[1][0] = mma(x1, y0, acc[1][0]);
         acc[1][1] = mma(x1, y1, acc[1][1]);
-        a2 = mma(tfrag<TK64>(smem + H_A1, 32 * s, T2, lane), tfrag<TK32>(smem + H_DZ2, 32 * s, Tn2, lane), a2);
+        a2 = mma(tfrag<TK64>(smem + H_A1, 32 * s, T2, ln), tfrag<TK32>(smem + H_DZ2, 32 * s, Tn2, ln), a2);
       }
 #pragma unroll
       for (int x = 0; x < 2; ++x)
 #pragma unroll
         for (int y = 0; y < 2; ++y)
           if (!ABL(K, ABL_HEADUPD))
-            tile_adam(st.blk[2 * x + y], hm[2 * x + y], hv[2 * x + y], HW1, Ta + x, Tb + y, lane, acc[x][y], K, smem);
-      if (!ABL(K, ABL_HEADUPD)) tile_adam(st.t2, hm[4], hv[4], HW2, T2, Tn2, lane, a2, K, smem);
+            tile_adam(st.blk[2 * x + y], hm[2 * x + y], hv[2 * x + y], HW1, Ta + x, Tb + y, ln, acc[x][y], K, smem);
+      if (!ABL(K, ABL_HEADUPD)) tile_adam(st.t2, hm[4], hv[4], HW2, T2, Tn2, ln, a2, K, smem);
       if (tid < H_NVEC) {
         // the 8 waves' partial sums in a fixed order: bit-reproducible whatever order the waves ran in
-        const LDS_AS float* c = ldsf(smem, H_PART) + tid;
+        // (one lane address, rebuilt here, for the partials and the entry: H_PART follows H_VEC; held across the step
+        // as two hoisted addresses, one of them went to scratch)
+        int t = tid;
+        asm volatile("" : "+v"(t));
+        LDS_AS float* ve = ldsf(smem, H_VEC) + t;
+        const LDS_AS float* c = ve + H_NVEC;
+        static_assert(H_PART == H_VEC + H_NVEC * 4, "the partial sums follow the vector");
         float gsum = c[0];
 #pragma unroll
         for (int w8 = 1; w8 < 8; ++w8) gsum += c[w8 * H_NVEC];
         float vm = hm[5][0], vvv = hm[5][1];
-        if (hvec_param(tid) >= 0) ldsf(smem, H_VEC)[tid] = adam1(st.vec.p, vm, vvv, gsum, K);
+        if (hvec_param(tid) >= 0) *ve = adam1(st.vec.p, vm, vvv, gsum, K);
         hm[5][0] = vm;
         hm[5][1] = vvv;
       }
@@ -1498,12 +1518,14 @@ __device__ __forceinline__ void head_main(const AflTfTrainArgs& a, int cid, ucha
   }
   // parameters back (a failed client keeps its pre-step values: the failing step applied no update)
   {
-    const int Ta = 2 * (wave & 3), Tb = 2 * (wave >> 2);
+    int ln = lane, wv = wave;
+    opq(ln, wv);  // (addresses recomputed here, not carried from the prologue's tile loads across the step loop)
+    const int Ta = 2 * (wv & 3), Tb = 2 * (wv >> 2);
 #pragma unroll
     for (int x = 0; x < 2; ++x)
 #pragma unroll
-      for (int y = 0; y < 2; ++y) tile_store(st.blk[2 * x + y], HW1, Ta + x, Tb + y, lane, P);
-    tile_store(st.t2, HW2, wave & 3, wave >> 2, lane, P);
+      for (int y = 0; y < 2; ++y) tile_store(st.blk[2 * x + y], HW1, Ta + x, Tb + y, ln, P);
+    tile_store(st.t2, HW2, wv & 3, wv >> 2, ln, P);
     if (tid < H_NVEC && hvec_param(tid) >= 0) P[hvec_param(tid)] = ar(st.vec.p);
   }
   if (tid == 0) {
