@@ -99,6 +99,9 @@ void bgemm(torch::Tensor A, torch::Tensor B, torch::Tensor Cm, c10::optional<tor
   g.M = M; g.N = N; g.K = K; g.nC = nC;
   g.act = act; g.gact = gact; g.accum = accum; g.splitk = std::max<int64_t>(1, splitk);
   g.alpha = (float)alpha;
+  // every split runs the whole epilogue on its partial sum: only the linear parts (alpha, dropout, act'(G)) commute
+  TORCH_CHECK(g.splitk == 1 || (g.accum == 2 && !g.bias && !g.Z && g.act == 0),
+              "bgemm: split-K needs accum = 2 and takes no bias, Z or activation");
   g.drop = make_drop(seeds, stepctl, layer, p);
   g.no_ts = generic ? 1 : 0;
   if (asum.has_value() && asum->defined()) {
@@ -146,6 +149,8 @@ void gather_icu(torch::Tensor rows, torch::Tensor idx, torch::Tensor stepctl, in
   dense(lab, "lab");
   dense(y, "y");
   TORCH_CHECK(rows.dim() == 2 && rows.size(1) == 24 && idx.dim() == 3, "rows [N, 24], idx [S, C, B]");
+  TORCH_CHECK(idx.size(0) >= 1, "gather_icu: idx needs at least one step");
+  TORCH_CHECK(stepctl.numel() >= 3, "gather_icu: stepctl = [step, min_bs, nan_abort]");
   const int C = idx.size(1), B = idx.size(2);
   TORCH_CHECK(vit.numel() == (long)C * B * 7 && lab.numel() == (long)C * B * 16 && y.numel() == (long)C * B,
               "output sizes");
@@ -162,6 +167,9 @@ void gather_har(torch::Tensor x, torch::Tensor y, torch::Tensor idx, torch::Tens
   dense(stepctl, "stepctl", torch::kInt32);
   dense(ox, "ox");
   dense(oy, "oy", torch::kInt64);
+  TORCH_CHECK(x.dim() == 2 && idx.dim() == 3 && y.numel() == x.size(0), "x [N, F], y [N], idx [S, C, B]");
+  TORCH_CHECK(idx.size(0) >= 1, "gather_har: idx needs at least one step");
+  TORCH_CHECK(stepctl.numel() >= 3, "gather_har: stepctl = [step, min_bs, nan_abort]");
   const int C = idx.size(1), B = idx.size(2), F = x.size(1);
   TORCH_CHECK(ox.numel() == (long)C * B * F && oy.numel() == (long)C * B, "output sizes");
   ok(afl_gather_har(x.data_ptr<float>(), (const long*)y.data_ptr<int64_t>(), F, idx.data_ptr<int>(),
@@ -450,11 +458,17 @@ void ln_fwd(torch::Tensor x, c10::optional<torch::Tensor> a, c10::optional<torch
   dev(beta, "beta");
   TORCH_CHECK(x.size(2) == 64 && x.stride(2) == 1 && y.stride(2) == 1, "LayerNorm rows of 64 contiguous columns");
   TORCH_CHECK(gamma.dim() == 2 && gamma.stride(1) == 1 && beta.stride(0) == gamma.stride(0), "gamma/beta [C, 64]");
+  TORCH_CHECK(beta.dim() == 2 && beta.stride(1) == 1 && gamma.size(0) == x.size(0) && beta.size(0) == x.size(0) &&
+                  gamma.size(1) >= 64 && beta.size(1) >= 64,
+              "ln_fwd: gamma/beta must be [C, >= 64] views with unit column stride");
+  TORCH_CHECK(y.size(0) == x.size(0) && y.size(1) == x.size(1) && y.size(2) == 64, "ln_fwd: y must be [C, rows, 64]");
+  TORCH_CHECK(stats.numel() == 2 * x.size(0) * x.size(1), "ln_fwd: stats must be [C, rows, 2]");
   AflLn l{};
   l.x = x.data_ptr<float>(); l.sXc = x.stride(0); l.sXr = x.stride(1);
   if (a.has_value() && a->defined()) {
     view3(*a, "a");
     TORCH_CHECK(a->stride(2) == 1, "a columns must be contiguous");
+    TORCH_CHECK(a->sizes() == x.sizes(), "ln_fwd: a must match x's shape");
     l.a = a->data_ptr<float>(); l.sAc = a->stride(0); l.sAr = a->stride(1);
   }
   if (s.has_value() && s->defined()) {
@@ -480,7 +494,18 @@ void ln_bwd(torch::Tensor dy, torch::Tensor s, torch::Tensor stats, torch::Tenso
   view3(dx, "dx");
   dense(stats, "stats");
   TORCH_CHECK(dy.stride(2) == 1 && s.stride(2) == 1 && dx.stride(2) == 1, "contiguous columns");
+  dev(gamma, "gamma");
+  dev(dgamma, "dgamma");
+  dev(dbeta, "dbeta");
+  TORCH_CHECK(gamma.dim() == 2 && dgamma.dim() == 2 && dbeta.dim() == 2, "ln_bwd: gamma/dgamma/dbeta must be 2-D");
   TORCH_CHECK(dgamma.stride(0) == gamma.stride(0) && dbeta.stride(0) == gamma.stride(0), "param/grad strides");
+  TORCH_CHECK(gamma.stride(1) == 1 && dgamma.stride(1) == 1 && dbeta.stride(1) == 1 && gamma.size(0) == dy.size(0) &&
+                  dgamma.size(0) == dy.size(0) && dbeta.size(0) == dy.size(0) && gamma.size(1) >= 64 &&
+                  dgamma.size(1) >= 64 && dbeta.size(1) >= 64,
+              "ln_bwd: gamma/dgamma/dbeta must be [C, >= 64] views with unit column stride");
+  TORCH_CHECK(dy.size(2) == 64 && s.sizes() == dy.sizes() && dx.sizes() == dy.sizes(),
+              "ln_bwd: dy, s and dx must all be [C, rows, 64]");
+  TORCH_CHECK(stats.numel() == 2 * dy.size(0) * dy.size(1), "ln_bwd: stats must be [C, rows, 2]");
   AflLnB l{};
   l.dy = dy.data_ptr<float>(); l.sDc = dy.stride(0); l.sDr = dy.stride(1);
   l.s = s.data_ptr<float>(); l.sSc = s.stride(0); l.sSr = s.stride(1);
@@ -489,6 +514,8 @@ void ln_bwd(torch::Tensor dy, torch::Tensor s, torch::Tensor stats, torch::Tenso
   l.dx = dx.data_ptr<float>(); l.sXc = dx.stride(0); l.sXr = dx.stride(1); l.dx_accum = (int)dx_accum;
   if (da.has_value() && da->defined()) {
     view3(*da, "da");
+    TORCH_CHECK(da->stride(2) == 1 && da->sizes() == dy.sizes(),
+                "ln_bwd: da must be [C, rows, 64] with unit column stride");
     l.da = da->data_ptr<float>(); l.sAc = da->stride(0); l.sAr = da->stride(1);
   }
   l.dgamma = dgamma.data_ptr<float>(); l.dbeta = dbeta.data_ptr<float>();
@@ -505,7 +532,11 @@ void gru_fwd(torch::Tensor gi, torch::Tensor bhh, torch::Tensor h, int64_t col0)
   dev(bhh, "bhh");
   view3(h, "h");
   const int C = gi.size(0), B = gi.size(1);
-  TORCH_CHECK(gi.size(2) == 96 && bhh.stride(1) == 1 && h.stride(2) == 1, "gru shapes");
+  TORCH_CHECK(gi.dim() == 3 && gi.size(2) == 96 && bhh.dim() == 2 && bhh.stride(1) == 1 && h.stride(2) == 1,
+              "gru shapes");
+  TORCH_CHECK(bhh.size(0) == C && bhh.size(1) >= 96, "gru_fwd: bhh must be [C, >= 96]");
+  TORCH_CHECK(h.size(0) == C && h.size(1) == B && col0 >= 0 && h.size(2) >= col0 + 32,
+              "gru_fwd: h must be [C, B, >= col0 + 32]");
   ok(afl_gru_fwd(gi.data_ptr<float>(), bhh.data_ptr<float>(), bhh.stride(0), C, B, h.data_ptr<float>(), h.stride(0),
                  h.stride(1), col0, cur()),
      "gru_fwd");
@@ -516,8 +547,19 @@ void gru_bwd(torch::Tensor dh, int64_t col0, torch::Tensor gi, torch::Tensor bhh
   view3(dh, "dh");
   dense(gi, "gi");
   dense(dgi, "dgi");
+  dev(bhh, "bhh");
+  dev(dbih, "dbih");
+  dev(dbhh, "dbhh");
+  TORCH_CHECK(gi.dim() == 3 && gi.size(2) == 96 && bhh.dim() == 2 && dbih.dim() == 2 && dbhh.dim() == 2, "gru shapes");
   TORCH_CHECK(dbih.stride(0) == bhh.stride(0) && dbhh.stride(0) == bhh.stride(0), "grad strides");
   const int C = gi.size(0), B = gi.size(1);
+  TORCH_CHECK(bhh.stride(1) == 1 && dbih.stride(1) == 1 && dbhh.stride(1) == 1 && bhh.size(0) == C &&
+                  dbih.size(0) == C && dbhh.size(0) == C && bhh.size(1) >= 96 && dbih.size(1) >= 96 &&
+                  dbhh.size(1) >= 96,
+              "gru_bwd: bhh and the bias gradients must be [C, >= 96] views with unit column stride");
+  TORCH_CHECK(dh.stride(2) == 1 && dh.size(0) == C && dh.size(1) == B && col0 >= 0 && dh.size(2) >= col0 + 32,
+              "gru_bwd: dh must be [C, B, >= col0 + 32]");
+  TORCH_CHECK(dgi.numel() == gi.numel(), "gru_bwd: dgi must be [C, B, 96]");
   ok(afl_gru_bwd(dh.data_ptr<float>(), dh.stride(0), dh.stride(1), col0, gi.data_ptr<float>(), bhh.data_ptr<float>(),
                  bhh.stride(0), C, B, dgi.data_ptr<float>(), dbih.data_ptr<float>(), dbhh.data_ptr<float>(), cur()),
      "gru_bwd");
@@ -534,7 +576,14 @@ void bce(torch::Tensor z, torch::Tensor y, torch::Tensor bsz, torch::Tensor epoc
   dense(failed, "failed", torch::kInt32);
   dense(losses, "losses");
   dense(dz, "dz");
+  TORCH_CHECK(bsz.dim() == 2 && bsz.size(1) >= 1, "bce: bsz [S, C]");
   const int S = bsz.size(0), C = bsz.size(1), B = z.numel() / C;
+  TORCH_CHECK(z.numel() == (long)C * B && y.numel() == z.numel() && dz.numel() == z.numel(),
+              "bce: z, y and dz must each hold C * B values");
+  TORCH_CHECK(epoch.sizes() == bsz.sizes(), "bce: epoch must have bsz's shape [S, C]");
+  TORCH_CHECK(nb.numel() == C && failed.numel() == C, "bce: nb and failed must have length C");
+  TORCH_CHECK(stepctl.numel() >= 3, "bce: stepctl = [step, min_bs, nan_abort]");
+  TORCH_CHECK(losses.dim() == 2 && losses.size(0) == C, "bce: losses [C, E]");
   ok(afl_bce(z.data_ptr<float>(), y.data_ptr<float>(), bsz.data_ptr<int>(), epoch.data_ptr<int>(), nb.data_ptr<int>(),
              stepctl.data_ptr<int>(), C, B, S, failed.data_ptr<int>(), losses.data_ptr<float>(), losses.size(1),
              dz.data_ptr<float>(), cur()),
@@ -552,7 +601,15 @@ void ce(torch::Tensor logits, torch::Tensor y, torch::Tensor bsz, torch::Tensor 
   dense(failed, "failed", torch::kInt32);
   dense(losses, "losses");
   dense(dz, "dz");
+  TORCH_CHECK(bsz.dim() == 2 && bsz.size(1) >= 1 && logits.dim() >= 1 && logits.size(-1) >= 1,
+              "ce: bsz [S, C], logits [.., K]");
   const int S = bsz.size(0), C = bsz.size(1), K = logits.size(-1), B = logits.numel() / ((long)C * K);
+  TORCH_CHECK(logits.numel() == (long)C * B * K && y.numel() == (long)C * B && dz.numel() == logits.numel(),
+              "ce: logits / dz must hold C * B * K values and y C * B");
+  TORCH_CHECK(epoch.sizes() == bsz.sizes(), "ce: epoch must have bsz's shape [S, C]");
+  TORCH_CHECK(nb.numel() == C && failed.numel() == C, "ce: nb and failed must have length C");
+  TORCH_CHECK(stepctl.numel() >= 3, "ce: stepctl = [step, min_bs, nan_abort]");
+  TORCH_CHECK(losses.dim() == 2 && losses.size(0) == C, "ce: losses [C, E]");
   ok(afl_ce(logits.data_ptr<float>(), (const long*)y.data_ptr<int64_t>(), K, bsz.data_ptr<int>(), epoch.data_ptr<int>(),
             nb.data_ptr<int>(), stepctl.data_ptr<int>(), C, B, S, failed.data_ptr<int>(), losses.data_ptr<float>(),
             losses.size(1), dz.data_ptr<float>(), cur()),
@@ -587,7 +644,13 @@ void conv_pe_fwd(torch::Tensor x, torch::Tensor params, int64_t w_off, int64_t b
   dense(x, "x");
   dense(params, "params");
   dense(h, "h");
+  TORCH_CHECK(x.dim() == 3 && params.dim() == 2 && params.size(0) == x.size(0),
+              "conv_pe_fwd: x [C, B, L], params [C, P]");
   const int C = x.size(0), B = x.size(1), L = x.size(2);
+  TORCH_CHECK(h.numel() == (long)C * B * L * 64, "conv_pe_fwd: h must be [C, B*L, 64]");
+  TORCH_CHECK(w_off >= 0 && b_off >= 0 && pe_off >= 0 && w_off + 192 <= params.size(1) &&
+                  b_off + 64 <= params.size(1) && pe_off + 64L * L <= params.size(1),
+              "conv_pe_fwd: weight / bias / positional-encoding ranges must lie within a params row");
   ok(afl_conv_pe_fwd(x.data_ptr<float>(), C, B, L, params.data_ptr<float>(), params.size(1), w_off, b_off, pe_off,
                      h.data_ptr<float>(), cur()),
      "conv_pe_fwd");
@@ -597,7 +660,11 @@ void conv_pe_bwd(torch::Tensor x, torch::Tensor dh, torch::Tensor grads, int64_t
   dense(x, "x");
   dense(dh, "dh");
   dense(grads, "grads");
+  TORCH_CHECK(x.dim() == 3 && grads.dim() == 2 && grads.size(0) == x.size(0), "conv_pe_bwd: x [C, B, L], grads [C, P]");
   const int C = x.size(0), B = x.size(1), L = x.size(2);
+  TORCH_CHECK(dh.numel() == (long)C * B * L * 64, "conv_pe_bwd: dh must be [C, B*L, 64]");
+  TORCH_CHECK(w_off >= 0 && b_off >= 0 && w_off + 192 <= grads.size(1) && b_off + 64 <= grads.size(1),
+              "conv_pe_bwd: weight / bias ranges must lie within a grads row");
   auto ws = torch::empty({afl_conv_pe_bwd_ws_floats(C, B, L)}, x.options());  // ordered partials
   ok(afl_conv_pe_bwd(x.data_ptr<float>(), dh.data_ptr<float>(), C, B, L, grads.data_ptr<float>(), grads.size(1), w_off,
                      b_off, cur(), ws.data_ptr<float>()),
@@ -607,12 +674,18 @@ void conv_pe_bwd(torch::Tensor x, torch::Tensor dh, torch::Tensor grads, int64_t
 void mean_rows_fwd(torch::Tensor h, int64_t B, int64_t L, torch::Tensor out) {
   dense(h, "h");
   dense(out, "out");
+  TORCH_CHECK(B >= 1 && L >= 1 && h.dim() >= 1 && h.numel() == h.size(0) * B * L * 64 &&
+                  out.numel() == h.size(0) * B * 64,
+              "mean_rows_fwd: h [C, B*L, 64], out [C, B, 64]");
   ok(afl_mean_rows_fwd(h.data_ptr<float>(), h.size(0), B, L, out.data_ptr<float>(), cur()), "mean_rows_fwd");
 }
 
 void mean_rows_bwd(torch::Tensor dout, int64_t B, int64_t L, torch::Tensor dh) {
   dense(dout, "dout");
   dense(dh, "dh");
+  TORCH_CHECK(B >= 1 && L >= 1 && dout.dim() >= 1 && dout.numel() == dout.size(0) * B * 64 &&
+                  dh.numel() == dout.size(0) * B * L * 64,
+              "mean_rows_bwd: dout [C, B, 64], dh [C, B*L, 64]");
   ok(afl_mean_rows_bwd(dout.data_ptr<float>(), dout.size(0), B, L, dh.data_ptr<float>(), cur()), "mean_rows_bwd");
 }
 
