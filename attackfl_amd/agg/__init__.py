@@ -15,11 +15,12 @@ Each rule returns ``AggResult(params [P] | None, ok, info)``.  Rows are in clien
   norm clip + cosine filter + FedAvg of the kept originals
 * fltracer      ``src/Utils.py:359-369`` (dormant in the reference)  PCA(1) + MAD z-score
 * byzantine     ``src/Utils.py:218-248`` (dead code in the reference) cosine ≥ 0.9 to model 0
-Beyond the reference (docs/PARITY.md): multi_krum, bulyan (assumed Byzantine count ``byz-f``) and geomed (RFA).
+Beyond the reference (docs/PARITY.md): multi_krum, bulyan, dnc (assumed Byzantine count ``byz-f``) and geomed (RFA).
 FLTrust and the hypernetwork live in the engine (``fl/engine.py`` ``_fltrust``, ``fl/hyper_server.py``): they train.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 from typing import Dict, Optional, Union
 
@@ -154,6 +155,28 @@ def geomed(U: torch.Tensor, sizes=None, geomed_iters: int = 100, geomed_nu: floa
     return AggResult(ops.weighted_rows(U, w), True, {"weights": w, "iters": iters, "objective": obj})
 
 
+def dnc(U: torch.Tensor, sizes=None, byz_f="auto", dnc_iters: int = 1, dnc_sub_dim: int = 10000, dnc_c: float = 1.0,
+        seed: int = 0, **_) -> AggResult:
+    """Divide-and-Conquer (Shejwalkar & Houmansadr, NDSS 2021; beyond the reference, rule text in docs/PARITY.md):
+    ``dnc_iters`` times, the Gram of the rows on ``dnc_sub_dim`` keyed random columns (all of them in natural order
+    when that is >= P), scores lambda_1 u_i^2 from its top eigenpair, the drop = min(ceil(c f), n - 1) rows with the
+    largest (score, index) dropped; the size-weighted mean of the rows kept in every iteration (of all rows when none
+    is).  Device, n <= 64: three launches for any ``dnc_iters`` (``k_dnc_gram``, ``k_dnc_select``, ``weighted_rows``);
+    no host read.  drop = 0 is FedAvg itself."""
+    n = U.shape[0]
+    f = byzantine_count(n, byz_f, 2, "dnc")
+    iters, b, c = int(dnc_iters), int(dnc_sub_dim), float(dnc_c)
+    if iters < 1 or b < 1 or not c > 0:
+        raise ValueError(f"dnc needs dnc-iters >= 1, dnc-sub-dim >= 1 and dnc-c > 0 (got {dnc_iters}, {dnc_sub_dim}, "
+                         f"{dnc_c}).")
+    drop = min(math.ceil(c * f), n - 1)
+    s = torch.ones(n, dtype=torch.float64) if sizes is None else sizes
+    s = _device_weights(s, U.device)
+    keep, scores, w = ops.dnc_filter(U, b, iters, seed, drop, s)
+    out = ops.fedavg(U, s) if drop == 0 else ops.weighted_rows(U, w)
+    return AggResult(out, True, {"selected": keep, "f": f, "drop": drop, "scores": scores})
+
+
 def shieldfl(U: torch.Tensor, sizes=None, **_) -> AggResult:
     norms = ops.row_norms(U).to(U.device)
     Un = U / (norms.to(U.dtype)[:, None] + 1e-8)
@@ -258,6 +281,7 @@ AGGREGATORS = {
     "multi_krum": multi_krum,
     "bulyan": bulyan,
     "geomed": geomed,
+    "dnc": dnc,
     "shieldfl": shieldfl,
     "gmm": gmm,
     "scionfl": scionfl,

@@ -21,9 +21,9 @@ Extensions (all optional, defaults keep reference behaviour):
   synthetic: auto | true | false   (auto = use the reference pickles when present)
   train-size / test-size / seed / har-train-size / har-test-size
 ``server:``
-  mode: the reference's modes plus multi_krum | bulyan | geomed (Multi-Krum, Bulyan and the geometric median /
-        RFA: defences that assume f >= 1 Byzantine clients; ``krum`` keeps the reference's f = 0, A-11; definitions
-        in docs/PARITY.md)
+  mode: the reference's modes plus multi_krum | bulyan | geomed | dnc (Multi-Krum, Bulyan, the geometric median /
+        RFA and Divide-and-Conquer: defences that assume f >= 1 Byzantine clients; ``krum`` keeps the reference's
+        f = 0, A-11; definitions in docs/PARITY.md)
 ``engine:``
   trainer: auto | fused | graph | eager | oracle  (fused = HIP persistent TransformerModel / RNNModel
                                     kernels; graph = HIP-graph-replayed layer programs for CNN/RNN/HAR models;
@@ -47,12 +47,16 @@ Extensions (all optional, defaults keep reference behaviour):
   fault-inject: [{client, round}]   (NaN-poison a client's model before that training round)
   gmm-rank: int                     (gmm mode's PCA rank, default 1; 0 = max(1, min(4, n // 2 - 1)), the
                                     round-5 rule: profiles/gmm_rank_study_r6.md)
-  byz-f: auto | int >= 0            (multi_krum / bulyan: the assumed number f of Byzantine clients; auto =
+  byz-f: auto | int >= 0            (multi_krum / bulyan / dnc: the assumed number f of Byzantine clients; auto =
                                     max(0, (n - 3) // 4), the largest f Bulyan admits; an explicit f >= 1 needs
-                                    n >= 2 f + 3 (multi_krum) or n >= 4 f + 3 (bulyan) or the round raises)
+                                    n >= 2 f + 3 (multi_krum, dnc) or n >= 4 f + 3 (bulyan) or the round raises;
+                                    dnc drops min(ceil(dnc-c f), n - 1) rows per iteration)
   geomed-iters: int >= 1            (geomed: at most that many smoothed-Weiszfeld iterations, default 100; fewer
                                     once the objective moves by <= 1e-9 of itself)
   geomed-nu: float > 0              (geomed: the smoothing floor of the distances, default 1e-6, the RFA value)
+  dnc-iters: int >= 1               (dnc: independent column sub-samples whose keep masks are intersected, default 1)
+  dnc-sub-dim: int >= 1             (dnc: columns per sub-sample, default 10000; >= P uses every column)
+  dnc-c: float > 0                  (dnc: the filtering fraction, ceil(c f) rows dropped per iteration, default 1.0)
   save-state: bool                  (write {model}.state.pt + {model}.clients.r{rank}.pt every round)
   resume: bool                      (continue from those files: counters, RNGs, optimizer moments)
 """
@@ -66,7 +70,7 @@ from typing import Any, Dict, List, Optional
 import yaml
 
 SERVER_MODES = ("fedavg", "hyper", "FLTrust", "trimmed_mean", "shieldfl", "gmm", "krum", "median", "scionfl",
-                "fltracer", "byzantine", "multi_krum", "bulyan", "geomed")
+                "fltracer", "byzantine", "multi_krum", "bulyan", "geomed", "dnc")
 ATTACK_MODES = ("Random", "Min-Max", "Min-Sum", "Opt-Fang", "LIE")
 MODEL_NAMES = ("CNNModel", "RNNModel", "TransformerModel", "TransformerClassifier")
 DATA_NAMES = ("ICU", "HAR", "CIFAR10")
@@ -102,7 +106,8 @@ EXTENSION_DEFAULTS: Dict[str, Any] = {
                "async-checkpoint": True, "compat-hyper-resume": False, "compat-fltrust": False, "max-retries": 50, "trace": False,
                "phase-sync": False, "fault-inject": [], "save-state": False, "resume": False,
                "speculative": True, "compat-har-train": False, "compat-fedavg-alias": False, "gmm-rank": 1,
-               "byz-f": "auto", "geomed-iters": 100, "geomed-nu": 1e-6},
+               "byz-f": "auto", "geomed-iters": 100, "geomed-nu": 1e-6, "dnc-iters": 1, "dnc-sub-dim": 10000,
+               "dnc-c": 1.0},
 }
 
 
@@ -269,6 +274,17 @@ class Config:
             nu_ok = False
         if not nu_ok:
             raise ValueError(f"engine.geomed-nu must be a number > 0 (got {nu!r})")
+        for key, default in (("dnc-iters", 1), ("dnc-sub-dim", 10000)):
+            v = self.engine.get(key, default)
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"engine.{key} must be an integer >= 1 (got {v!r})")
+        c = self.engine.get("dnc-c", 1.0)
+        try:
+            c_ok = not isinstance(c, bool) and float(c) > 0
+        except (TypeError, ValueError):
+            c_ok = False
+        if not c_ok:
+            raise ValueError(f"engine.dnc-c must be a number > 0 (got {c!r})")
         return self
 
     def to_dict(self) -> Dict[str, Any]:

@@ -361,6 +361,53 @@ def top_pc(G: torch.Tensor, sweeps: int = 12) -> torch.Tensor:
     return composite.top_pc(G)
 
 
+def _seed64(seed: int) -> int:
+    """A 64-bit seed as the signed integer the bindings take."""
+    s = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return s - (1 << 64) if s & (1 << 63) else s
+
+
+def _dnc_native(t: torch.Tensor, n: int) -> bool:
+    return _dev(t) and 1 <= n <= 64
+
+
+def dnc_columns(P: int, b: int, t: int, seed: int) -> torch.Tensor:
+    """Columns of DnC iteration ``t`` in summation order (the host mirror of ``k_dnc_gram``'s keyed Feistel map)."""
+    return composite.dnc_columns(P, b, t, seed)
+
+
+def dnc_gram(U: torch.Tensor, b: int, iters: int, seed: int) -> torch.Tensor:
+    """[iters, n, n] fp64 Grams of the rows over each iteration's ``b`` keyed columns, centred on the column mean.
+    Device, n <= 64: ``k_dnc_gram`` + the double centring of ``k_dnc_select``."""
+    if _dnc_native(U, U.shape[0]):
+        ones = torch.ones(U.shape[0], dtype=torch.float64, device=U.device)
+        return native().dnc_run(U.to(torch.float32).contiguous(), int(b), int(iters), _seed64(seed), 0, ones, False)[3]
+    return composite.dnc_gram(U, int(b), int(iters), seed)
+
+
+def dnc_select(G: torch.Tensor, drop: int, w: torch.Tensor, centre: bool = False):
+    """DnC scores, ranked drop and mask intersection on centred Grams [iters, n, n] -> (keep [n] bool, scores
+    [iters, n] fp64, weights [n] fp64 = w keep / sum).  Device, n <= 64: ``k_dnc_select`` (one launch, no host read)."""
+    G = G[None] if G.dim() == 2 else G
+    if _dnc_native(G, G.shape[1]):
+        keep, scores, weights, _ = native().dnc_run(G.to(torch.float64).contiguous(), 0, 0, 0, int(drop),
+                                                    w.to(device=G.device, dtype=torch.float64).contiguous(),
+                                                    bool(centre))
+        return keep.bool(), scores, weights
+    return composite.dnc_select(G, int(drop), w, bool(centre))
+
+
+def dnc_filter(U: torch.Tensor, b: int, iters: int, seed: int, drop: int, w: torch.Tensor):
+    """``dnc_select(dnc_gram(U, ...), drop, w)``; on the device (n <= 64) two launches for any ``iters``: the Gram
+    partials go straight into the select kernel."""
+    if _dnc_native(U, U.shape[0]):
+        keep, scores, weights, _ = native().dnc_run(U.to(torch.float32).contiguous(), int(b), int(iters), _seed64(seed),
+                                                    int(drop), w.to(device=U.device, dtype=torch.float64).contiguous(),
+                                                    False)
+        return keep.bool(), scores, weights
+    return composite.dnc_select(composite.dnc_gram(U, int(b), int(iters), seed), int(drop), w)
+
+
 def row_norms(U: torch.Tensor) -> torch.Tensor:
     if _dev(U):
         return native().row_dots(U.contiguous(), U.new_zeros(0), 0)[:, 0].clamp_min(0).sqrt()

@@ -516,3 +516,66 @@ def philox_normal(n: int, seed: int):
 def noise(own: torch.Tensor, sigma: float, seed: int) -> torch.Tensor:
     z = torch.from_numpy(philox_normal(own.numel(), int(seed) & 0xFFFFFFFFFFFFFFFF)).to(torch.float32)
     return own + float(sigma) * z.reshape(own.shape).to(own.device)
+
+
+# ---------------------------------------------------------------- DnC (docs/PARITY.md)
+def dnc_keys(seed: int, t: int):
+    """The two Feistel keys of DnC iteration ``t`` from the round's seed (mirror of plan_perm.h ``pl_dnc_keys``; the
+    one place the derivation is written down on the Python side)."""
+    from ..fl.trainers import _M32, _mix_i
+
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    a, b = _mix_i((seed & _M32) ^ 0x2545F491), _mix_i((seed >> 32) ^ 0x7F4A7C15)
+    return _mix_i(a ^ ((0x165667B1 * (t + 1)) & _M32)), _mix_i((b + 0xD3A2646C * (t + 1)) & _M32)
+
+
+def dnc_columns(P: int, b: int, t: int, seed: int) -> torch.Tensor:
+    """Columns of DnC iteration ``t`` in summation (position) order, int64 [min(b, P)]: all of 0..P-1 in natural order
+    when b >= P, else pi_t(0..b-1), pi_t the keyed Feistel permutation of [0, P) (bit-for-bit ``k_dnc_gram``'s)."""
+    from ..fl.trainers import _perm_t
+
+    P, b = int(P), int(b)
+    if P < 1 or b < 1:
+        raise ValueError(f"dnc_columns needs P >= 1 and b >= 1 (got {P}, {b})")
+    i = torch.arange(min(b, P), dtype=torch.int64)
+    if b >= P:
+        return i
+    k0, k1 = dnc_keys(seed, t)
+    return _perm_t(i, P, k0, k1)
+
+
+def dnc_gram(U: torch.Tensor, b: int, iters: int, seed: int) -> torch.Tensor:
+    """[iters, n, n] fp64: per iteration the Gram of the sub-sampled rows centred on their column mean."""
+    out = []
+    for t in range(int(iters)):
+        X = U.index_select(1, dnc_columns(U.shape[1], b, t, seed).to(U.device)).double()
+        Xc = X - X.mean(dim=0, keepdim=True)
+        out.append(Xc @ Xc.t())
+    return torch.stack(out)
+
+
+def dnc_select(G: torch.Tensor, drop: int, w: torch.Tensor, centre: bool = False):
+    """DnC's select-and-intersect on the centred Grams ``G [iters, n, n]`` (``k_dnc_select``): scores
+    s_t[i] = lambda_1 u_i^2 of the top eigenpair, the ``drop`` rows with the largest (score, index) dropped per
+    iteration (NaN = +inf; on a tie the higher index goes), the masks ANDed, every row kept when none survives ->
+    (keep [n] bool, scores [iters, n] fp64, weights [n] fp64 = w keep / sum).  ``centre``: double-centre G first.
+    Tensor ops only (no host read), so it also serves device tensors beyond the kernel's 64 rows."""
+    G = G.double()
+    G = G[None] if G.dim() == 2 else G
+    n = G.shape[1]
+    if centre:
+        G = G - G.mean(dim=1, keepdim=True) - G.mean(dim=2, keepdim=True) + G.mean(dim=(1, 2), keepdim=True)
+    fin = torch.isfinite(G)
+    bad = ~fin.all(dim=2).all(dim=1)  # a non-finite Gram: every score of the iteration is NaN
+    ev, V = torch.linalg.eigh(torch.where(fin, G, torch.zeros_like(G)))
+    u = V[:, :, -1]
+    s = ev[:, -1].clamp_min(0.0)[:, None] * (u * u)
+    s = torch.where(bad[:, None], torch.full_like(s, float("nan")), s)
+    key = torch.where(torch.isnan(s), torch.full_like(s, float("inf")), s)
+    idx = torch.arange(n, device=G.device)
+    above = (key[:, None, :] > key[:, :, None]) | ((key[:, None, :] == key[:, :, None]) & (idx[None, :] > idx[:, None]))
+    keep_t = above.sum(dim=2) >= int(drop)  # [iters, n]: row i stays when >= drop rows rank above it
+    keep = keep_t.all(dim=0)
+    keep = torch.where(keep.any(), keep, torch.ones_like(keep))
+    wk = w.to(device=G.device, dtype=torch.float64) * keep.double()
+    return keep, s, wk / wk.sum()

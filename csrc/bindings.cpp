@@ -120,6 +120,53 @@ torch::Tensor top_pc(torch::Tensor G, int64_t sweeps) {
   return z;
 }
 
+// DnC (agg.dnc; agg.hip k_dnc_gram / k_dnc_select).  dnc_run: src = U [n <= 64, P] fp32 (the Gram launch, then the
+// select launch on its partials) or src = G [iters, n, n] fp64 (the select launch alone, double-centring G first when
+// ``centre``) -> (keep [n] uint8, scores [iters, n], weights [n] = w keep / sum, the centred Grams [iters, n, n])
+std::vector<torch::Tensor> dnc_run(torch::Tensor src, int64_t b, int64_t iters, int64_t seed, int64_t drop,
+                                   torch::Tensor w, bool centre) {
+  check_dev(w, "w", torch::kFloat64);
+  const bool rows = src.scalar_type() == torch::kFloat32;
+  check_dev(src, rows ? "U" : "G", rows ? torch::kFloat32 : torch::kFloat64);
+  int64_t n;
+  if (rows) {
+    TORCH_CHECK(src.dim() == 2 && src.size(0) >= 1 && src.size(0) <= 64 && src.size(1) >= 1 &&
+                    src.size(1) <= (int64_t)INT_MAX, "dnc: U [n <= 64, P < 2^31]");
+    TORCH_CHECK(b >= 1 && iters >= 1 && iters <= 65535, "dnc: b >= 1 and 1 <= iters <= 65535 (got ", b, ", ", iters, ")");
+    n = src.size(0);
+  } else {
+    TORCH_CHECK(src.dim() == 3 && src.size(0) >= 1 && src.size(1) >= 1 && src.size(1) <= 64 &&
+                    src.size(2) == src.size(1), "dnc_select: G [iters, n, n], n <= 64");
+    n = src.size(1);
+    iters = src.size(0);
+  }
+  TORCH_CHECK(w.numel() == n && drop >= 0 && drop <= n - 1, "dnc: w [n] and 0 <= drop <= n - 1 (got n = ", n,
+              ", drop = ", drop, ")");
+  auto opt = w.options();
+  auto keep = torch::zeros({n}, opt.dtype(torch::kUInt8));
+  auto scores = torch::zeros({iters, n}, opt);
+  auto weights = torch::zeros({n}, opt);
+  auto gout = torch::empty({iters, n, n}, opt);
+  const double* in = nullptr;
+  int nb = 0;
+  torch::Tensor partial;
+  if (rows) {
+    const long P = src.size(1);
+    partial = torch::empty({afl_dnc_partials((int)n, P, b, (int)iters)}, opt);
+    TORCH_CHECK(afl_dnc_gram(src.data_ptr<float>(), (int)n, P, b, (int)iters, (uint64_t)seed,
+                             partial.data_ptr<double>(), cur()) == 0, "dnc_gram launch failed");
+    in = partial.data_ptr<double>();
+    nb = afl_dnc_nblocks(P, b);
+  } else {
+    in = src.data_ptr<double>();
+  }
+  TORCH_CHECK(afl_dnc_select(in, nb, (int)n, (int)iters, centre ? 1 : 0, (int)drop, w.data_ptr<double>(),
+                             keep.data_ptr<uint8_t>(), scores.data_ptr<double>(), weights.data_ptr<double>(),
+                             gout.data_ptr<double>(), cur()) == 0, "dnc_select launch failed");
+  AFL_CHECK_LAUNCH();
+  return {keep, scores, weights, gout};
+}
+
 // Krum selection (agg.multi_krum / agg.bulyan): D [n, n] fp64 -> (sel [rounds] int32 in selection order, mask [n]
 // uint8, first-pass scores [n] fp64)
 std::vector<torch::Tensor> krum_select(torch::Tensor D, int64_t f, int64_t rounds, bool iterated) {
@@ -858,6 +905,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gmm_filter", &gmm_filter, pybind11::arg("G"), pybind11::arg("att"), pybind11::arg("rank") = 0);
   m.def("top_pc", &top_pc);
   m.def("krum_select", &krum_select);
+  m.def("dnc_run", &dnc_run);
   m.def("bulyan_coord", &bulyan_coord);
   m.def("geomed_weights", &geomed_weights);
   m.def("fxsum_test", &fxsum_test);

@@ -110,6 +110,16 @@ int run_selftest() {
         if (seen[v]++) return fail("pl_perm not injective", (long)v, (long)n);
       }
       checked += n;
+      // the DnC column map (agg.hip k_dnc_gram): the first b = n / 2 + 1 positions of pi_t are distinct and in range
+      for (int t = 0; t < 2; ++t) {
+        const DncKeys d = pl_dnc_keys(seed, t);
+        seen.assign(n, 0);
+        for (uint32_t i = 0; i < n / 2 + 1; ++i) {
+          const uint32_t v = pl_perm(i, n, h, d.k0, d.k1);
+          if (v >= n) return fail("dnc column out of range", (long)v, (long)n);
+          if (seen[v]++) return fail("dnc column repeated", (long)v, (long)n);
+        }
+      }
     }
   }
   // afl_keep: the 16-bit halves of one hash must give two independent-looking columns; check the

@@ -444,6 +444,18 @@ int afl_bulyan_coord(const float* U, int N, long P, const int* sel, int theta, i
 // simplex -> w [n] fp64, info = {iterations, objective}
 int afl_geomed_weights(const double* G, const double* alpha, int n, int iters, double nu, double* w, double* info,
                        hipStream_t s);
+// Divide-and-Conquer (DnC, docs/PARITY.md) on U [K <= 64][P] fp32.  afl_dnc_gram (agg.hip k_dnc_gram): for each of
+// ``iters`` iterations the tile-pair partials of the Gram of the rows centred on row 0, over the b keyed columns of
+// that iteration (all P in natural order when b >= P) -> partial, afl_dnc_partials(K, P, b, iters) doubles.
+// afl_dnc_select (k_dnc_select): per iteration the centred Gram (nb > 0: src = those partials of nb blocks, summed and
+// double-centred; nb = 0: src = Grams [iters][n][n], double-centred when ``centre``), the top eigenpair, scores
+// lambda_1 u_i^2, the ``drop`` largest (score, index) dropped; the masks ANDed (all rows when none survives) ->
+// keep [n] 0/1, scores [iters][n], weights [n] = w keep / sum, gout [iters][n][n] the centred Grams
+int afl_dnc_nblocks(long P, long b);  // blocks (position chunks) per iteration
+long afl_dnc_partials(int K, long P, long b, int iters);
+int afl_dnc_gram(const float* U, int K, long P, long b, int iters, uint64_t seed, double* partial, hipStream_t s);
+int afl_dnc_select(const double* src, int nb, int n, int iters, int centre, int drop, const double* w,
+                   unsigned char* keep, double* scores, double* weights, double* gout, hipStream_t s);
 void afl_noise_philox(const float* own, float* out, long P, float sigma, uint64_t seed, hipStream_t s);
 
 // comm.hip — one-shot intra-node all-gather over IPC-mapped peer buffers (xGMI)

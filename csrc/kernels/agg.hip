@@ -14,11 +14,14 @@
 //   krum_select     Multi-Krum ranking / Bulyan iterated selection on the distance matrix (beyond the reference)
 //   bulyan_coord    Bulyan's mean of the beta values closest to the column median, over selected rows
 //   geomed_weights  smoothed Weiszfeld (geometric median, RFA) in Gram space
+//   dnc_gram        DnC: fp64-MFMA Grams over keyed random column subsets, all iterations in one launch
+//   dnc_select      DnC: top eigenpair, scores, ranked drop, mask intersection and weights, one wave
 //
 // Every reduction is two-pass with a fixed summation order (no float atomics), so results are
 // bit-identical across ranks: the replicated server state on each rank stays in lock-step.
 #include "common.h"
 #include "kernels.h"
+#include "plan_perm.h"
 
 // ============================================================================ colstats
 __global__ void __launch_bounds__(256) k_colstats(const float* __restrict__ G, int K, long P, float* __restrict__ mean,
@@ -928,18 +931,15 @@ int afl_gmm_filter(const double* G, int n, const unsigned char* att, unsigned ch
 // sequential rotations (the rotation's fp64 divide / square-root chain and three barriers were the kernel's whole
 // time: 158 us per call).  (Repeated squaring of G, the round-4 form, let the second eigenvector leak in at
 // (lambda_2 / lambda_1)^(2^squarings): 2 % at a 0.999 ratio, 66 % at 0.9999 — nearly iid updates.)
-__global__ void __launch_bounds__(64) k_top_pc(const double* __restrict__ G, int n, int sweeps, double* __restrict__ z) {
-  __shared__ double A[GMM_MAXN * GMM_MAXN], V[GMM_MAXN * GMM_MAXN];
-  __shared__ double cs_c[GMM_MAXN / 2], cs_s[GMM_MAXN / 2];
-  __shared__ int cs_p[GMM_MAXN / 2], cs_q[GMM_MAXN / 2];
+// The Jacobi body, shared by k_top_pc and k_dnc_select (one 64-lane block): A [n][n] symmetric and V = I in LDS, filled
+// and synchronised by the caller; on return A's diagonal holds the eigenvalues, V's columns the eigenvectors, and the
+// result is the index of the largest eigenvalue (first maximum; every lane returns the same).
+__device__ __forceinline__ int jacobi_top(double* __restrict__ A, double* __restrict__ V, double* __restrict__ cs_c,
+                                          double* __restrict__ cs_s, int* __restrict__ cs_p, int* __restrict__ cs_q,
+                                          int n, int sweeps) {
   const int k = threadIdx.x;
-  for (int e = k; e < n * n; e += blockDim.x) {
-    A[e] = G[e];
-    V[e] = (e / n == e % n) ? 1.0 : 0.0;
-  }
   const int m = n + (n & 1);  // (an odd n pairs one index with the dummy index n each step: skipped)
   const int half = m / 2;
-  __syncthreads();
   for (int sweep = 0; sweep < sweeps; ++sweep) {
     {  // converged to fp64 precision (off-diagonal mass <= 1e-32 of the diagonal's): the remaining rotations
        // would be identities up to rounding, so the sweep count is an upper bound (uniform decision)
@@ -1008,12 +1008,205 @@ __global__ void __launch_bounds__(64) k_top_pc(const double* __restrict__ G, int
   int top = 0;
   for (int i = 1; i < n; ++i)
     if (A[i * n + i] > A[top * n + top]) top = i;
+  return top;
+}
+
+__global__ void __launch_bounds__(64) k_top_pc(const double* __restrict__ G, int n, int sweeps, double* __restrict__ z) {
+  __shared__ double A[GMM_MAXN * GMM_MAXN], V[GMM_MAXN * GMM_MAXN];
+  __shared__ double cs_c[GMM_MAXN / 2], cs_s[GMM_MAXN / 2];
+  __shared__ int cs_p[GMM_MAXN / 2], cs_q[GMM_MAXN / 2];
+  const int k = threadIdx.x;
+  for (int e = k; e < n * n; e += blockDim.x) {
+    A[e] = G[e];
+    V[e] = (e / n == e % n) ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  const int top = jacobi_top(A, V, cs_c, cs_s, cs_p, cs_q, n, sweeps);
   if (k < n) z[k] = V[k * n + top] * sqrt(fmax(A[top * n + top], 0.0));
 }
 
 int afl_top_pc(const double* G, int n, int sweeps, double* z, hipStream_t s) {
   if (n < 1 || n > GMM_MAXN || sweeps < 1) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_top_pc, dim3(1), dim3(64), 0, s, G, n, sweeps, z);
+  return (int)hipGetLastError();
+}
+
+// ============================================================================ DnC
+// Divide-and-Conquer (Shejwalkar & Houmansadr, NDSS 2021; beyond the reference, rule text in docs/PARITY.md): for each
+// of ``iters`` iterations a spectral filter on b keyed random columns.  Two launches for all iterations together.
+//
+// k_dnc_gram: grid (position chunks of GR_CH, iters).  Position i of iteration t is column pi_t(i) (plan_perm.h
+// pl_perm with pl_dnc_keys(seed, t)), or i itself when b >= P (``natural``); positions >= nv = min(b, P) contribute
+// zeros.  Each step of a wave covers 16 positions: lane l derives the column of position (l & 15) once, the four
+// columns of its group come over by __shfl, and the rest is k_gram_f64 (rows centred on row 0 in fp64, the same
+// MFMA / C-D layout / fixed-order cross-wave reduction) with gathered 4-byte loads.  A column index is < P by
+// construction (the cycle walk ends in [0, P); nv <= P), a row index is checked against K.
+template <int T>
+__global__ void __launch_bounds__(256) k_dnc_gram(const float* __restrict__ G, int K, long P, long nv, int natural,
+                                                  uint64_t seed, double* __restrict__ partial) {
+  constexpr int NP = T * (T + 1) / 2;
+  __shared__ double red[4][NP * 256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r16 = lane & 15, grp = lane >> 4;
+  const DncKeys key = pl_dnc_keys(seed, (int)blockIdx.y);
+  const int half = pl_half_bits((uint32_t)P);
+  d4v acc[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) acc[p] = d4v{0.0, 0.0, 0.0, 0.0};
+  const long c_begin = (long)blockIdx.x * GR_CH + wave * (GR_CH / 4);
+  for (int st = 0; st < GR_CH / 4 / 16; ++st) {
+    if (c_begin + st * 16 >= nv) break;  // (wave-uniform: the remaining positions are all past b)
+    const long pos = c_begin + st * 16 + r16;
+    int mycol = -1;
+    if (pos < nv) mycol = natural ? (int)pos : (int)pl_perm((uint32_t)pos, (uint32_t)P, half, key.k0, key.k1);
+    int col[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) col[q] = __shfl(mycol, grp * 4 + q, 64);
+    double x[T][4];
+    double ctr[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) ctr[q] = col[q] >= 0 ? (double)G[col[q]] : 0.0;  // the centre row (row 0)
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      const int row = t * 16 + r16;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        x[t][q] = (row < K && col[q] >= 0) ? (double)G[(long)row * P + col[q]] - ctr[q] : 0.0;
+    }
+    int p = 0;
+#pragma unroll
+    for (int ti = 0; ti < T; ++ti)
+#pragma unroll
+      for (int tj = ti; tj < T; ++tj, ++p)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[ti][q], x[tj][q], acc[p], 0, 0, 0);
+  }
+  // fixed-order reduction over the 4 waves
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wave][p * 256 + (grp + 4 * r) * 16 + r16] = acc[p][r];
+  __syncthreads();
+  double* out = partial + ((long)blockIdx.y * gridDim.x + blockIdx.x) * NP * 256;
+  for (int e = threadIdx.x; e < NP * 256; e += 256) out[e] = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
+}
+
+int afl_dnc_nblocks(long P, long b) { return (int)afl_cdiv(b < P ? b : P, GR_CH); }
+
+long afl_dnc_partials(int K, long P, long b, int iters) {
+  const int T = (K + 15) / 16;
+  return (long)iters * afl_dnc_nblocks(P, b) * (T * (T + 1) / 2) * 256;
+}
+
+int afl_dnc_gram(const float* U, int K, long P, long b, int iters, uint64_t seed, double* partial, hipStream_t s) {
+  // (P < 2^31: a column index is a uint32 of the permutation's domain and an int in the kernel)
+  if (K < 1 || K > GR_MAXK || P < 1 || P > 0x7FFFFFFFl || b < 1 || iters < 1 || iters > 65535)
+    return (int)hipErrorInvalidValue;
+  const long nv = b < P ? b : P;
+  const int natural = b >= P ? 1 : 0;
+  const dim3 grid((unsigned)afl_cdiv(nv, GR_CH), (unsigned)iters);
+  switch ((K + 15) / 16) {
+    case 1: hipLaunchKernelGGL(k_dnc_gram<1>, grid, dim3(256), 0, s, U, K, P, nv, natural, seed, partial); break;
+    case 2: hipLaunchKernelGGL(k_dnc_gram<2>, grid, dim3(256), 0, s, U, K, P, nv, natural, seed, partial); break;
+    case 3: hipLaunchKernelGGL(k_dnc_gram<3>, grid, dim3(256), 0, s, U, K, P, nv, natural, seed, partial); break;
+    default: hipLaunchKernelGGL(k_dnc_gram<4>, grid, dim3(256), 0, s, U, K, P, nv, natural, seed, partial); break;
+  }
+  return (int)hipGetLastError();
+}
+
+// k_dnc_select: one wave, looping over the iterations (the masks are ANDed in registers: lane i owns row i).  Per
+// iteration: the Gram H of the rows centred on row 0 — the block partials summed in block order (nb > 0), or read as
+// it is (nb = 0) —, double-centred C = H - rowmean - colmean + mean (each mean a sum in index order; skipped when
+// nb = 0 and !centre) and written to gout; jacobi_top; score_i = lambda_1 u_i^2 (lambda_1 floored at 0); row i is
+// dropped when fewer than ``drop`` rows have a larger (score, index), a NaN score counting as +inf — exactly ``drop``
+// rows whatever the scores hold, and on an exact tie the higher index.  After the last iteration: no row kept -> every
+// row kept; weights = w keep / sum (summed in index order).  Every loop has a fixed trip count (Jacobi: <= DNC_SWEEPS).
+constexpr int DNC_SWEEPS = 16;
+
+__global__ void __launch_bounds__(64) k_dnc_select(const double* __restrict__ src, int nb, int n, int iters, int centre,
+                                                   int drop, const double* __restrict__ w,
+                                                   unsigned char* __restrict__ keep, double* __restrict__ scores,
+                                                   double* __restrict__ weights, double* __restrict__ gout) {
+  __shared__ double A[GMM_MAXN * GMM_MAXN], V[GMM_MAXN * GMM_MAXN];
+  __shared__ double cs_c[GMM_MAXN / 2], cs_s[GMM_MAXN / 2];
+  __shared__ int cs_p[GMM_MAXN / 2], cs_q[GMM_MAXN / 2];
+  __shared__ double vec[GMM_MAXN];
+  const int k = threadIdx.x;
+  const int T = (n + 15) / 16, NP = T * (T + 1) / 2;
+  bool kept = k < n;
+  for (int t = 0; t < iters; ++t) {
+    if (nb > 0) {
+      const double* part = src + (long)t * nb * NP * 256;
+      for (int e = k; e < NP * 256; e += 64) {
+        int p = e >> 8, ti = 0;  // tile pair index -> (ti, tj)
+        while (p >= T - ti) { p -= T - ti; ++ti; }
+        const int tj = ti + p;
+        const int i = ti * 16 + ((e & 255) >> 4), j = tj * 16 + (e & 15);
+        if (i > j || j >= n) continue;  // (the upper triangle stands for both halves: one writer per entry)
+        double a = 0.0;
+        for (int b = 0; b < nb; ++b) a += part[(long)b * NP * 256 + e];
+        A[i * n + j] = a;
+        A[j * n + i] = a;
+      }
+    } else {
+      for (int e = k; e < n * n; e += 64) A[e] = src[(long)t * n * n + e];
+    }
+    __syncthreads();
+    if (nb > 0 || centre) {
+      double rm = 0.0;
+      if (k < n) {
+        for (int j = 0; j < n; ++j) rm += A[k * n + j];
+        rm /= (double)n;
+        vec[k] = rm;
+      }
+      __syncthreads();
+      double mean = 0.0;
+      for (int j = 0; j < n; ++j) mean += vec[j];
+      mean /= (double)n;
+      // H is symmetric, so column j's mean is row j's; the two means are added first so that C stays symmetric
+      for (int e = k; e < n * n; e += 64) A[e] = A[e] - (vec[e / n] + vec[e % n]) + mean;
+      __syncthreads();
+    }
+    for (int e = k; e < n * n; e += 64) {
+      gout[(long)t * n * n + e] = A[e];
+      V[e] = (e / n == e % n) ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    const int top = jacobi_top(A, V, cs_c, cs_s, cs_p, cs_q, n, DNC_SWEEPS);
+    const double lam = A[top * n + top];
+    double sc = 0.0;
+    if (k < n) {
+      const double u = V[k * n + top];
+      sc = (lam < 0.0 ? 0.0 : lam) * (u * u);
+      scores[(long)t * n + k] = sc;
+      vec[k] = sc != sc ? INFINITY : sc;
+    }
+    __syncthreads();
+    if (k < n) {
+      const double mine = vec[k];
+      int above = 0;
+      for (int j = 0; j < n; ++j) above += (vec[j] > mine || (vec[j] == mine && j > k)) ? 1 : 0;
+      kept = kept && above >= drop;
+    }
+    __syncthreads();
+  }
+  if (__ballot(kept) == 0ull) kept = k < n;  // the empty intersection keeps every row
+  if (k < n) vec[k] = kept ? w[k] : 0.0;
+  __syncthreads();
+  double sum = 0.0;
+  for (int j = 0; j < n; ++j) sum += vec[j];
+  if (k < n) {
+    keep[k] = kept ? 1 : 0;
+    weights[k] = vec[k] / sum;
+  }
+}
+
+int afl_dnc_select(const double* src, int nb, int n, int iters, int centre, int drop, const double* w,
+                   unsigned char* keep, double* scores, double* weights, double* gout, hipStream_t s) {
+  if (n < 1 || n > GMM_MAXN || iters < 1 || nb < 0 || drop < 0 || drop > n - 1) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_dnc_select, dim3(1), dim3(64), 0, s, src, nb, n, iters, centre, drop, w, keep, scores, weights,
+                     gout);
   return (int)hipGetLastError();
 }
 

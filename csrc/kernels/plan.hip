@@ -7,48 +7,15 @@
 // Both are 6-round balanced Feistel networks on the smallest even bit-width domain covering n, with
 // cycle walking back into [0, n) (a bijection of [0, 2^k) restricted to [0, n) by walking the cycle).
 // No sort, no host work: one launch builds the whole [C, E, maxnd] plan.  The integer math is
-// mirrored bit-for-bit by attackfl_amd/fl/trainers.py:_feistel_plan (CPU branch); the helpers are
-// __host__ __device__ so csrc/host/host_check.hip can run them under ASan/UBSan on the CPU.
+// mirrored bit-for-bit by attackfl_amd/fl/trainers.py:_feistel_plan (CPU branch); the helpers (the permutation
+// itself in plan_perm.h, shared with agg.hip) are __host__ __device__ so csrc/host/host_check.hip can run them under
+// ASan/UBSan on the CPU.
 #include <algorithm>
 #include "common.h"
 #include "kernels.h"
+#include "plan_perm.h"
 
 namespace {
-
-__host__ __device__ __forceinline__ uint32_t pl_mix(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x85EBCA6Bu;
-  x ^= x >> 13;
-  x *= 0xC2B2AE35u;
-  x ^= x >> 16;
-  return x;
-}
-
-__host__ __device__ __forceinline__ uint32_t pl_feistel(uint32_t x, int half, uint32_t mask, uint32_t k0, uint32_t k1) {
-  uint32_t L = x >> half, R = x & mask;
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    const uint32_t F = pl_mix(R ^ k0 ^ (k1 + 0x9E3779B9u * (uint32_t)(r + 1))) & mask;
-    const uint32_t nL = R;
-    R = L ^ F;
-    L = nL;
-  }
-  return (L << half) | R;
-}
-
-__host__ __device__ __forceinline__ uint32_t pl_perm(uint32_t x, uint32_t n, int half, uint32_t k0, uint32_t k1) {
-  const uint32_t mask = (1u << half) - 1u;
-  do {
-    x = pl_feistel(x, half, mask, k0, k1);
-  } while (x >= n);
-  return x;
-}
-
-__host__ __device__ __forceinline__ int pl_half_bits(uint32_t n) {
-  int k = 2;
-  while ((1ull << k) < (unsigned long long)n) k += 2;
-  return k / 2;
-}
 
 // subset keys (s0, s1) of a client seed and shuffle keys (e0, e1) of its epoch e
 struct PlanKeys {
