@@ -48,7 +48,7 @@ from ..utils import trace
 from ..utils.ckpt import CheckpointWriter
 from ..utils.log import Logger, MetricsWriter, NullLogger, print_with_color
 from .hyper_server import HyperServer
-from .trainers import Plan, make_plan, make_trainer
+from .trainers import Pending, Plan, make_plan, make_trainer
 
 # every rule of AGGREGATORS runs on the device without a host read (gmm up to 64 rows; its success is a device
 # bool): with one of them the aggregate and the next round's launch are enqueued before the host waits for the
@@ -130,7 +130,6 @@ class LocalClient:
     rng: random.Random
     seed: int
     training_round: int = 0
-    has_model: bool = False
     genuine: Optional[torch.Tensor] = None     # last received genuine models [K, P]
 
 
@@ -149,6 +148,51 @@ def build_client_table(cfg: Config, world: int, attackers: Optional[Dict[int, At
     return table
 
 
+@dataclass(slots=True)
+class Prepared:
+    """Host half of a launch (``FLEngine._prepare_local``).  The fields from ``dec`` on are staged for those attack
+    decisions by ``FLEngine._stage``, and staged again if an attacker's first attack round flips them."""
+    tq: float                                # host clock when the preparation began
+    meta: np.ndarray                         # [slots, META + E] host mirror of the block's meta columns and losses
+    clients: List[tuple]                     # (local row, client, LocalClient, num_data) of every started client
+    js: List[int]                            # their local rows
+    faults: List[int]                        # local rows poisoned with NaN before this training (fault injection)
+    selected: tuple                          # the selection it was prepared for
+    dec: tuple = ()                          # per started client: attacks instead of training
+    train_rows: Optional[List[int]] = None   # local rows in the training launch (attackers ride along with 0 rows)
+    train_seeds: Optional[List[int]] = None  # their dropout seeds
+    meta_d: Optional[torch.Tensor] = None    # meta[:, :META] on the device
+    js_d: Optional[torch.Tensor] = None      # js on the device
+    rows_d: Optional[torch.Tensor] = None    # train_rows on the device
+    tseed_d: Optional[torch.Tensor] = None   # train_seeds on the device, in the trainer's int32 form
+    plan: Optional[Plan] = None              # the training rows' sampling plan (None: nobody trains)
+    fedavg_w: Optional[torch.Tensor] = None  # one rank, every selected row stored: FedAvg weights on the device
+    sizes_h: Optional[torch.Tensor] = None   # one rank: the selected clients' sizes (fp64, host)
+    tq1: float = 0.0                         # host clock at the start of the staging, and after its upload
+    tq2: float = 0.0
+    staged_ev: Optional["torch.cuda.Event"] = None  # staged on the staging stream: the launch waits for this
+
+
+@dataclass(slots=True)
+class Launch:
+    """Device half of a launch (``FLEngine._enqueue_local``) and, once ``_finish_local`` ran, its outcome: the
+    meta mirror ``prep.meta`` completed with the ok flags and losses, the filled ``block``, ``lw_times``."""
+    prep: Prepared
+    block: Optional[torch.Tensor]            # this rank's update block [slots, W]; None: plain rows
+    plain: bool                              # one rank, all trained in place: local_params ARE the update rows
+    in_place: bool                           # every local client is in the launch: local_params trained in place
+    params: Optional[torch.Tensor]           # the rows handed to the trainer (None: nobody trains)
+    pending: Optional[Pending]               # the training launch (None: nobody trains)
+    attack_jobs: List[tuple]                 # (local row, client, LocalClient, AttackSpec) of this round's attacks
+    ready: Optional["torch.cuda.Event"]      # the attackers' inputs are complete (before the training launch)
+    t_enqueue: float                         # host time from the enqueue's start to the training launch
+    t_launch: float                          # host time of the training launch itself
+    atk_out: Optional[List[tuple]] = None    # (local row, ok, malicious update); None until _finish_attacks ran
+    tw: float = 0.0                          # host clock before and after the attacks
+    tp2: float = 0.0
+    lw_times: Optional[Dict[str, float]] = None  # the round record's t_lw_* entries
+
+
 @dataclass
 class EarlyLaunch:
     """An early launch (``FLEngine._early_launch``): what its server step reported and what undoing it needs."""
@@ -156,7 +200,7 @@ class EarlyLaunch:
     fl_old: Optional[torch.Tensor]           # FLTrust's server model before the step
     hyper_step: Optional[int]                # the hypernetwork's step count before the step
     snap: tuple                              # (per local client (rng state, training round, genuine), server rng state)
-    prep: Optional[dict]                     # the next launch's host half, staged ahead
+    prep: Optional[Prepared]                 # the next launch's host half, staged ahead
     info: dict = field(default_factory=dict)  # the server step's info
     rule_ok: Optional[tuple] = None          # gmm: (pinned bool, event) of the filter's success
     keep: Optional[List[int]] = None         # with attackers: the genuine rows stored, and the pool made of them
@@ -183,6 +227,7 @@ class FLEngine:
                  device=None, leader: Optional[bool] = None, verbose: bool = True, train_dataset=None,
                  test_dataset=None):
         _LIVE.add(self)
+        self._closed = False  # (before anything below can raise: the exit hook closes half-built engines too)
         self.cfg = cfg
         self.comm = comm or LoopbackComm(device or "cpu")
         self.device = torch.device(device) if device is not None else self.comm.device
@@ -264,7 +309,6 @@ class FLEngine:
         # fault injection: [{client: i, round: r}] -> client i's model is NaN-poisoned before
         # its local training of training-round r, which fails that client and retries the FL round
         self.faults = {(int(f["client"]), int(f["round"])) for f in (cfg.engine.get("fault-inject") or [])}
-        self._phase_t: Dict[str, float] = {}
         # FedAvg fast path: with no attacker and no detection, the server needs only
         # sum_i s_i w_i and sum_i s_i -> ONE all_reduce of [P + 5] (+ #failed, #reported, the decision word and its
         # square) instead of the [N, P] all-gather
@@ -279,15 +323,17 @@ class FLEngine:
         # relaunches exactly the same client work (no detection, START from the in-memory global model /
         # hypernetwork; attackers draw from the pool set before the launch), no resume sidecars.  Any world
         # size: validation is replicated, so no rank waits for another's decision before the next launch.
-        self._spec = None
-        self._next_prep = None  # the next launch's host half, staged while the current training runs
-        self._fedavg_w = None
-        self._val_stream = None
-        self._start_ready = None
+        self._spec: Optional[Launch] = None  # the next round's launch, enqueued ahead (speculative / early)
+        self._next_prep: Optional[Prepared] = None  # the next launch's host half, staged while this training runs
+        self._start_ready = None  # event: the latest launch's START models are generated (the validation stream waits)
+        self._attack_info = self._trust = None  # the round in progress: the last attack's info, FLTrust's scores
+        self._fl_pending = None  # FLTrust's server-model training, checked at the round's end
         self._sel_cache = None
-        self._meta_host = None
-        self._plain_rows = False
-        self._pending = None
+        self._rows_idx: dict = {}  # _take_rows: index lists already on the device
+        self._staging = Staging(self.device)
+        # created on first use: GPU streams, the meta read's pinned buffer, FLTrust's root set, hyper's checkpoint tail
+        self._val_stream = self._side = self._stage_stream = None
+        self._meta_pinned = self._fl_root = self._hyper_tail = None
         self._has_attackers = any(ci.attack is not None for ci in self.table)
         self._speculative = (bool(cfg.engine.get("speculative", True)) and self.device.type == "cuda"
                              and not cfg.hyper_detection.get("enable", False) and not cfg.load_parameters
@@ -349,7 +395,7 @@ class FLEngine:
         if self.mode == "hyper":
             hnet = self.hyper.hnet
             # deferred: the arena's copy is issued after the next training launch (utils/ckpt.py)
-            if getattr(self, "_hyper_tail", None) is None:
+            if self._hyper_tail is None:
                 self._hyper_tail = hnet.target_tail()
             self.ckpt_writer.submit("hyper", hnet.arena, lambda a: hnet.state_dict_of(a, clone=False),
                                     self._pth(True), defer=True, tail=self._hyper_tail)
@@ -467,7 +513,7 @@ class FLEngine:
         from ..ops.layers import upload
 
         key = tuple(idx)
-        cache = self.__dict__.setdefault("_rows_idx", {})
+        cache = self._rows_idx
         ix = cache.get(key)
         if ix is None:
             if len(cache) > 1024:
@@ -483,32 +529,22 @@ class FLEngine:
         ds = getattr(self.trainer, "device_seed", None)
         return ds if (ds is not None and self.device.type == "cuda") else _no_dev_seed
 
-    @property
-    def _staging(self) -> "Staging":
-        st = getattr(self, "_staging_obj", None)
-        if st is None:
-            st = self._staging_obj = Staging(self.device)
-        return st
-
     def _side_stream(self):
         if self.device.type != "cuda":
             return None
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = torch.cuda.Stream(self.device)
         return self._side
 
-    def _local_work(self, genuine: Dict[int, Optional[torch.Tensor]]) -> torch.Tensor:
-        return self._finish_local(self._launch_local(genuine))
-
-    def _launch_local(self, genuine: Dict[int, Optional[torch.Tensor]]) -> dict:
+    def _launch_local(self, genuine: Dict[int, Optional[torch.Tensor]]) -> Launch:
         """Prepare this rank's clients for the round and enqueue the genuine clients' training (async).
         Uses the preparation staged ahead by ``run_round`` when there is one."""
         prep, self._next_prep = self._next_prep, None
-        if prep is None or prep["selected"] != tuple(self.selected):
+        if prep is None or prep.selected != tuple(self.selected):
             prep = self._prepare_local()
         return self._enqueue_local(prep, genuine)
 
-    def _prepare_local(self) -> dict:
+    def _prepare_local(self) -> Prepared:
         """Host half of a launch — client counters, the data draws, fault injection, the plan — none of which
         depends on the previous round's outcome, so ``run_round`` stages the NEXT launch's half before it
         waits for the current training (the draws are the same whenever they happen: one per launch, in
@@ -533,42 +569,39 @@ class FLEngine:
             meta[j, 2] = float(num_data)
             meta[j, 3] = 1.0 if lc.info.attack is not None else 0.0
             clients.append((j, i, lc, num_data))
-        prep = {"tq": tq, "meta": meta, "clients": clients, "faults": faults, "selected": tuple(self.selected)}
+        prep = Prepared(tq, meta, clients, [j for j, _, _, _ in clients], faults, tuple(self.selected))
         self._stage(prep, self._attack_decisions(prep))
         return prep
 
-    def _prepare_staged(self) -> dict:
+    def _prepare_staged(self) -> Prepared:
         """``_prepare_local`` with its device half (the upload and the plan kernel) on a staging stream: those
         depend on nothing the running training writes, and on the compute stream they sat behind it, in the gap
         between two training kernels.  The launch waits for the staging event (``_enqueue_local``)."""
         dev = self.device
         if dev.type != "cuda":
             return self._prepare_local()
-        if getattr(self, "_stage_stream", None) is None:
+        if self._stage_stream is None:
             self._stage_stream = torch.cuda.Stream(device=dev)
         main = torch.cuda.current_stream(dev)
         with torch.cuda.stream(self._stage_stream):
             prep = self._prepare_local()
-            ev = torch.cuda.Event()
-            ev.record(self._stage_stream)
-        plan = prep.get("plan")
-        if plan is not None and plan.order.is_cuda:
-            plan.order.record_stream(main)  # (allocated on the staging stream, read by the launch on main)
-        prep["staged_ev"] = ev
+            prep.staged_ev = torch.cuda.Event()
+            prep.staged_ev.record(self._stage_stream)
+        if prep.plan is not None and prep.plan.order.is_cuda:
+            prep.plan.order.record_stream(main)  # (allocated on the staging stream, read by the launch on main)
         return prep
 
     @staticmethod
-    def _attack_decisions(prep: dict) -> tuple:
+    def _attack_decisions(prep: Prepared) -> tuple:
         return tuple(lc.info.attack is not None and lc.training_round >= lc.info.attack.round
-                     and lc.genuine is not None and lc.genuine.shape[0] > 0 for _, _, lc, _ in prep["clients"])
+                     and lc.genuine is not None and lc.genuine.shape[0] > 0 for _, _, lc, _ in prep.clients)
 
-    def _stage(self, prep: dict, decisions: tuple) -> None:
+    def _stage(self, prep: Prepared, decisions: tuple) -> None:
         """Training rows / sizes / seeds for the given attack decisions, their ONE upload and the plan."""
         cfg, dev = self.cfg, self.device
-        tq1 = time.perf_counter()
-        train_rows, train_nd, train_seeds = [], [], []
-        attack_rows = []
-        for (j, i, lc, num_data), atk in zip(prep["clients"], decisions):
+        prep.dec, prep.tq1 = decisions, time.perf_counter()
+        train_rows, train_nd, train_seeds, attack_rows = [], [], [], []
+        for (j, i, lc, num_data), atk in zip(prep.clients, decisions):
             if atk:
                 attack_rows.append((j, lc))
             else:
@@ -589,48 +622,41 @@ class FLEngine:
             train_seeds = [train_seeds[k] for k in order]
         # FedAvg weights of the selected rows (single rank, every row stored): staged with the rest, so the
         # aggregate needs no host -> device copy after the training (== ops.fedavg's s / s.sum(), exact sums)
-        sel_nd = np.asarray([prep["meta"][r, 2] for r in self._local_rows()], np.float64) if self.world == 1 else None
+        sel_nd = np.asarray([prep.meta[r, 2] for r in self._local_rows()], np.float64) if self.world == 1 else None
         fw = sel_nd / sel_nd.sum() if sel_nd is not None and sel_nd.size and sel_nd.sum() > 0 else np.zeros(1)
         # every per-round host value the device needs goes up in ONE asynchronous copy (a pageable
         # torch.tensor(..., device=) per item was a blocking copy each: ~1.5 ms of host time per round)
-        js = [j for j, _, _, _ in prep["clients"]]
         plan_seeds = [sd * 1000003 + 17 for sd in train_seeds]
-        meta_d, js_d, rows_d, pseed_d, nd_d, tseed_d, fw_d = self._staging.upload([
-            prep["meta"][:, :META], np.asarray(js, np.int64), np.asarray(train_rows, np.int64),
+        prep.meta_d, prep.js_d, prep.rows_d, pseed_d, nd_d, prep.tseed_d, fw_d = self._staging.upload([
+            prep.meta[:, :META], np.asarray(prep.js, np.int64), np.asarray(train_rows, np.int64),
             np.asarray([(s & 0xFFFFFFFFFFFFFFFF) - (1 << 64) if (s & 0xFFFFFFFFFFFFFFFF) >= (1 << 63)
                         else (s & 0xFFFFFFFFFFFFFFFF) for s in plan_seeds], np.int64),
             np.asarray(train_nd, np.int32),
             np.asarray([self._dev_seed(s) for s in train_seeds], np.int32), fw])
-        tq2 = time.perf_counter()
-        plan = None
+        prep.tq2 = time.perf_counter()
+        prep.plan = None
         if train_rows:
-            plan = make_plan(self.train_table.n, train_nd, cfg.epoch, plan_seeds, dev,
-                             staged=(pseed_d, nd_d) if dev.type == "cuda" else None)
-        prep.update({"dec": decisions, "train_rows": train_rows, "train_seeds": train_seeds,
-                     "attack_rows": [j for j, _ in attack_rows], "js": js, "meta_d": meta_d, "js_d": js_d,
-                     "rows_d": rows_d, "tseed_d": tseed_d, "plan": plan,
-                     "fedavg_w": fw_d if sel_nd is not None and fw.size == len(self.selected) else None,
-                     "sizes_h": torch.from_numpy(sel_nd) if sel_nd is not None else None,
-                     "tq1": tq1, "tq2": tq2})
+            prep.plan = make_plan(self.train_table.n, train_nd, cfg.epoch, plan_seeds, dev,
+                                  staged=(pseed_d, nd_d) if dev.type == "cuda" else None)
+        prep.train_rows, prep.train_seeds = train_rows, train_seeds
+        prep.fedavg_w = fw_d if sel_nd is not None and fw.size == len(self.selected) else None
+        prep.sizes_h = torch.from_numpy(sel_nd) if sel_nd is not None else None
 
-    def _enqueue_local(self, prep: dict, genuine: Dict[int, Optional[torch.Tensor]]) -> dict:
+    def _enqueue_local(self, prep: Prepared, genuine: Dict[int, Optional[torch.Tensor]]) -> Launch:
         """Device half of a launch: START parameters, the update block, the training launch."""
-        cfg = self.cfg
-        dev = self.device
+        cfg, dev = self.cfg, self.device
         tq = time.perf_counter()
-        if prep.get("staged_ev") is not None:  # uploads / plan staged on the staging stream (_prepare_staged)
-            torch.cuda.current_stream(dev).wait_event(prep["staged_ev"])
-        for j, i, lc, _ in prep["clients"]:
+        if prep.staged_ev is not None:  # uploads / plan staged on the staging stream (_prepare_staged)
+            torch.cuda.current_stream(dev).wait_event(prep.staged_ev)
+        for j, i, lc, _ in prep.clients:
             g = genuine.get(i)
             if lc.info.attack is not None and g is not None and g.shape[0] > 0:
                 lc.genuine = g
         dec = self._attack_decisions(prep)
-        if dec != prep["dec"]:
+        if dec != prep.dec:
             self._stage(prep, dec)  # (an attacker's first attack round)
-        attack_jobs = [(j, i, lc, lc.info.attack) for (j, i, lc, _), a in zip(prep["clients"], dec) if a]
-        train_rows, train_seeds, js, js_d = prep["train_rows"], prep["train_seeds"], prep["js"], prep["js_d"]
-        rows_d = prep["rows_d"]
-        n_local = len(self.local)
+        attack_jobs = [(j, i, lc, lc.info.attack) for (j, i, lc, _), a in zip(prep.clients, dec) if a]
+        train_rows, js, n_local = prep.train_rows, prep.js, len(self.local)
         # the common case (every local client trains) trains local_params in place: no gather / scatter
         in_place = train_rows == list(range(n_local))
         # single rank, every local client in the launch (attackers with zero rows), trained in place: the round
@@ -639,53 +665,46 @@ class FLEngine:
         plain = (bool(train_rows) and in_place and self.world == 1 and not self.fast_fedavg
                  and self._local_rows() == list(range(n_local)))
         block = None if plain else torch.zeros(self.slots, self.W, dtype=torch.float32, device=dev)
-        tq2 = time.perf_counter()
         # START parameters of every started client (one batched generate / broadcast copy)
-        if prep["clients"]:
+        if prep.clients:
             if self.mode == "hyper":
-                start = self.hyper.generate_many([i for _, i, _, _ in prep["clients"]])
+                start = self.hyper.generate_many([i for _, i, _, _ in prep.clients])
             else:
-                p = self._start_params(prep["clients"][0][1])
+                p = self._start_params(prep.clients[0][1])
                 start = None if p is None else p[None, :].expand(len(js), -1)
             if start is not None:
                 if js == list(range(len(js))):
                     self.local_params[:len(js)].copy_(start)
                 else:
-                    self.local_params.index_copy_(0, js_d, start.contiguous())
+                    self.local_params.index_copy_(0, prep.js_d, start.contiguous())
         if self._speculative and dev.type == "cuda":
             # START is generated (hyper: the memoised generate_many validation reuses): a speculative
             # round's validation stream waits for this point, not for the training launched below
             self._start_ready = torch.cuda.Event()
             self._start_ready.record(torch.cuda.current_stream(dev))
-        for j in prep["faults"]:
+        for j in prep.faults:
             self.local_params[j, 0] = float("nan")
         if block is not None:
-            block[:, self.P:self.P + META] = prep["meta_d"]
+            block[:, self.P:self.P + META] = prep.meta_d
         tp0 = time.perf_counter()
-        pending = None
-        ready = None
+        params = pending = ready = None
         if attack_jobs and dev.type == "cuda":
             # the attackers' inputs are ready now; the side stream must not also wait for the training launch
             ready = torch.cuda.Event()
             ready.record(torch.cuda.current_stream(dev))
-        params = None
         if train_rows:
-            params = self.local_params if in_place else self.local_params.index_select(0, rows_d).contiguous()
-            pending = self.trainer.launch(params, prep["plan"], cfg.lr, cfg.batch_size, train_seeds,
-                                          seeds_dev=prep["tseed_d"] if self._dev_seed is not _no_dev_seed else None)
+            params = self.local_params if in_place else self.local_params.index_select(0, prep.rows_d).contiguous()
+            pending = self.trainer.launch(params, prep.plan, cfg.lr, cfg.batch_size, prep.train_seeds,
+                                          seeds_dev=prep.tseed_d if self._dev_seed is not _no_dev_seed else None)
         self.ckpt_writer.kick()  # last round's deferred checkpoint copy overlaps this round's training
-        tp1 = time.perf_counter()
-        return {"block": block, "attack_jobs": attack_jobs, "ready": ready, "pending": pending, "params": params,
-                "in_place": in_place, "rows_d": rows_d, "n_local": n_local, "meta": prep["meta"],
-                "train_rows": train_rows, "fedavg_w": prep["fedavg_w"], "sizes_h": prep.get("sizes_h"), "plain": plain,
-                "t": (prep["tq"], prep["tq1"], prep["tq2"], tp0, tp1), "t_enqueue": tp0 - tq}
+        return Launch(prep, block, plain, in_place, params, pending, attack_jobs, ready, t_enqueue=tp0 - tq,
+                      t_launch=time.perf_counter() - tp0)
 
-    def _finish_attacks(self, st: dict) -> None:
+    def _finish_attacks(self, launch: Launch) -> None:
         """Attackers' math on a side stream; their results replace their local_params rows (stream-ordered
         after the training launch, which read / wrote back their untouched models: no host wait)."""
-        attack_jobs, ready, pending, in_place = st["attack_jobs"], st["ready"], st["pending"], st["in_place"]
-        dev = self.device
-        tw = time.perf_counter()  # a speculative launch (run_round) may have been enqueued long before
+        attack_jobs, ready, dev = launch.attack_jobs, launch.ready, self.device
+        launch.tw = time.perf_counter()  # a speculative launch (run_round) may have been enqueued long before
         atk_out = []  # (row, ok, malicious update)
         if attack_jobs:
             # the attackers do not train: their math runs on a side stream while the genuine clients'
@@ -707,80 +726,57 @@ class FLEngine:
                                          f"{ {k: v for k, v in hi.items() if not isinstance(v, list)} }", "red")
             if side is not None:
                 torch.cuda.current_stream(dev).wait_stream(side)
-        if pending is not None and in_place:
+        if launch.pending is not None and launch.in_place:
             for j, ok, mal in atk_out:
                 if ok:
                     self.local_params[j].copy_(mal)
-        st["atk_out"], st["tw"], st["tp2"] = atk_out, tw, time.perf_counter()
+        launch.atk_out, launch.tp2 = atk_out, time.perf_counter()
 
-    def _finish_local(self, st: dict) -> Optional[torch.Tensor]:
-        """Attackers' math (``_finish_attacks``, unless done already), then wait for the training launch and
-        fill the update block (none at world 1 with plain rows)."""
-        if "atk_out" not in st:
-            self._finish_attacks(st)
-        block, pending = st["block"], st["pending"]
-        params, in_place, rows_d, n_local = st["params"], st["in_place"], st["rows_d"], st["n_local"]
-        tq, tq1, tq2, tp0, tp1 = st["t"]
-        atk_out, tw, tp2 = st["atk_out"], st["tw"], st["tp2"]
-        dev = self.device
-        hm = st["meta"]  # host mirror of the block's meta columns (ok filled in below): no device read needed
-        self._plain_rows = pending is not None and st["plain"]  # (_enqueue_local: no update block)
-        self._pending = pending
+    def _finish_local(self, launch: Launch) -> None:
+        """Attackers' math (``_finish_attacks``, unless done already), then wait for the training launch, complete
+        the host meta mirror and fill the update block (none at world 1 with plain rows)."""
+        if launch.atk_out is None:
+            self._finish_attacks(launch)
+        prep, block, pending, in_place = launch.prep, launch.block, launch.pending, launch.in_place
+        hm = prep.meta  # host mirror of the block's meta columns (ok filled in below): no device read needed
         P, E = self.P, self.E
         if pending is not None:
             ok_dev, loss_dev = pending.ok_device(), pending.losses_device()
             # world > 1: the ok flags and losses travel in the block and the host learns every rank's meta from
             # ONE read after the gather, so it does not wait for its own training here (one host round trip less)
-            host_wait = self.world == 1 or ok_dev is None or loss_dev is None
-            if host_wait:
+            if self.world == 1 or ok_dev is None or loss_dev is None:
                 oks, losses = pending.result()
-                for k, (j, o) in enumerate(zip(st["train_rows"], oks)):
+                for k, (j, o) in enumerate(zip(prep.train_rows, oks)):
                     hm[j, 1] = 1.0 if o else 0.0
                     hm[j, META:META + E] = np.asarray(losses[k], dtype=np.float32)[:E]
-            tp3 = time.perf_counter()
-            # A-15: an attacker still reports its num_data, ok = the attack's result (its row: _finish_attacks)
-            for j, ok, mal in atk_out:
-                hm[j, 1] = 1.0 if ok else 0.0
-            if self._plain_rows:
-                pass
-            elif in_place:
-                block[:n_local, :P] = self.local_params[:n_local]
-                if ok_dev is not None:
-                    block[:n_local, P + 1] = (ok_dev > 0).float()
-                else:
-                    block[:n_local, P + 1] = torch.tensor([1.0 if o else 0.0 for o in oks], device=dev)
-                block[:n_local, P + META:P + META + E] = (loss_dev if loss_dev is not None
-                                                         else losses.to(dev)).float()
-                for j, ok, _ in atk_out:
-                    block[j, P + 1] = 1.0 if ok else 0.0
-            else:
-                self.local_params.index_copy_(0, rows_d, params)
-                block[rows_d, :P] = params
-                okc = (ok_dev > 0).float() if ok_dev is not None else torch.tensor(
-                    [1.0 if o else 0.0 for o in oks], device=dev)
-                block[rows_d, P + 1] = okc
-                block[rows_d, P + META:P + META + E] = (loss_dev if loss_dev is not None else losses.to(dev)).float()
-                for j, ok, mal in atk_out:  # (only when no genuine client trains here: attackers are not launched)
-                    if ok:
-                        block[j, :P] = mal
-                    block[j, P + 1] = 1.0 if ok else 0.0
-        else:
-            tp3 = time.perf_counter()
-            for j, ok, mal in atk_out:  # every local client attacks: nothing was launched
-                hm[j, 1] = 1.0 if ok else 0.0
-                if ok:
+        tp3 = time.perf_counter()
+        if pending is not None and block is not None:
+            if in_place:  # the leading rows, as slice copies
+                rows, src = slice(0, len(self.local)), self.local_params[:len(self.local)]
+            else:  # a subset trained on gathered rows: back into the clients' models first
+                rows, src = prep.rows_d, launch.params
+                self.local_params.index_copy_(0, rows, src)
+            block[rows, :P] = src
+            block[rows, P + 1] = ((ok_dev > 0).float() if ok_dev is not None
+                                  else torch.tensor([1.0 if o else 0.0 for o in oks], device=self.device))
+            block[rows, P + META:P + META + E] = (loss_dev if loss_dev is not None
+                                                  else losses.to(self.device)).float()
+        # A-15: an attacker still reports its num_data, ok = the attack's result.  Its update is already in its
+        # local_params row when it rode along in place (_finish_attacks); otherwise nothing was launched for it
+        for j, ok, mal in launch.atk_out:
+            hm[j, 1] = 1.0 if ok else 0.0
+            if block is not None:
+                if ok and not in_place:
                     block[j, :P] = mal
                 block[j, P + 1] = 1.0 if ok else 0.0
         if block is not None:
             # every rank stamps its view of the replicated server state into its rows; the gather's reader checks
             # that all ranks agree (_check_decisions), so a rank whose validation / detection diverged fails loudly
             block[:, P + DECISION] = float(self._decision_word())
-        self._fedavg_w = st.get("fedavg_w")
-        self._lw_times = {"t_lw_prep": (tq2 - tq) + st.get("t_enqueue", 0.0), "t_lw_prep_host": tq1 - tq,
-                          "t_lw_prep_upload": tq2 - tq1, "t_lw_launch": tp1 - tp0, "t_lw_attack": tp2 - tw,
-                          "t_lw_wait": tp3 - tp2, "t_lw_post": time.perf_counter() - tp3}
-        self._meta_host = hm
-        return block
+        launch.lw_times = {"t_lw_prep": (prep.tq2 - prep.tq) + launch.t_enqueue, "t_lw_prep_host": prep.tq1 - prep.tq,
+                           "t_lw_prep_upload": prep.tq2 - prep.tq1, "t_lw_launch": launch.t_launch,
+                           "t_lw_attack": launch.tp2 - launch.tw, "t_lw_wait": tp3 - launch.tp2,
+                           "t_lw_post": time.perf_counter() - tp3}
 
     def _local_rows(self) -> List[int]:
         """Block rows of the selected clients (cached per selection)."""
@@ -852,11 +848,12 @@ class FLEngine:
                                              res.params.to(torch.float32), g_old)
         return info, rule_ok
 
-    def _aggregate(self, U: torch.Tensor, sizes: torch.Tensor, attackers: torch.Tensor, round_ok: bool) -> dict:
-        """The serial path: the host has read the round's meta."""
+    def _aggregate(self, U: torch.Tensor, sizes: torch.Tensor, attackers: torch.Tensor, round_ok: bool,
+                   w: Optional[torch.Tensor]) -> dict:
+        """The serial path: the host has read the round's meta.  ``w``: the FedAvg weights staged with the launch
+        (one rank, every row stored; the several-rank serial path weighs by the host sizes)."""
         if not round_ok:
             return {}
-        w = self._fedavg_w  # (one rank, every row stored; the several-rank serial path weighs by the host sizes)
         if w is not None and not (U.is_cuda and U.shape[0] == w.shape[0]):
             w = None
         return self._server_step(U, sizes, attackers, None, w=w)[0]
@@ -864,7 +861,7 @@ class FLEngine:
     def _fltrust_setup(self):
         """Root set (first 200 test rows, ``server.py:290-293``), its device table and the server model's
         trainer: built once and reused every round."""
-        if getattr(self, "_fl_root", None) is None:
+        if self._fl_root is None:
             from ..data import ICUData
 
             root = resolve_dataset(self.data_name, "test", self.cfg.data, verbose=False)
@@ -937,65 +934,31 @@ class FLEngine:
         self._attack_info = None
         self._trust = None
         with trace.range("fl/local"):
-            st, self._spec = self._spec, None
-            if st is None:
-                st = self._launch_local(self._genuine_for_attackers())
+            launch, self._spec = self._spec, None
+            if launch is None:
+                launch = self._launch_local(self._genuine_for_attackers())
             if self._speculative and self.rounds_left > 1 and not last and self._next_prep is None:
                 # the next launch's host half (draws, uploads, plan) while this round's training runs: after
                 # it, only the aggregate, START and the launch itself separate two training kernels
                 self._next_prep = self._prepare_staged()
-            esl = self._early_launch(st, last)
-            block = self._finish_local(st)
+            esl = self._early_launch(launch, last)
+            self._finish_local(launch)
             if self.phase_sync:  # stream-ordered otherwise: the timing-only sync is skipped
                 self._sync()
         t1 = time.perf_counter()
-        P = self.P
-        snapshot = None
+        U = snapshot = None
         stored = len(self.selected)
         if esl is not None:
             # one rank: the aggregate and the next launch went in before the wait (_early_launch)
-            U = None
-            meta = torch.from_numpy(self._meta_host[self._local_rows()])
+            meta = torch.from_numpy(launch.prep.meta[self._local_rows()])
             round_ok, info = self._early_outcome(esl, meta.numpy()[:, 1] > 0.5)
             t2 = t3 = time.perf_counter()
         elif self.fast_fedavg:
-            U = None
-            round_ok, meta = self._fedavg_allreduce(block)
+            round_ok, meta = self._fedavg_allreduce(launch.block, launch.prep.meta)
             info = {"path": "fedavg-allreduce"}
             t2 = t3 = time.perf_counter()
         else:
-            trace.push("fl/gather")
-            rows = self._local_rows()
-            idx = self._sel_cache[2]
-            if self.world == 1:  # every row is local: the host already knows the meta columns
-                meta = torch.from_numpy(self._meta_host[rows])
-                if self._plain_rows:
-                    U = self.local_params[:len(rows)]  # the trained models ARE the update rows: no block at all
-                else:
-                    U = self.comm.all_gather_rows(block).index_select(0, idx)[:, :P].contiguous()
-            else:
-                allb = self.comm.all_gather_rows(block)                    # [world*slots, W]
-                sel = allb.index_select(0, idx)
-                U = sel[:, :P].contiguous()
-                # the round's ONE host read: every client's [valid, result, size, attacker, decision | losses]; it
-                # is queued BEFORE the early launch and waited for through its own event, so the host waits for
-                # the gather (the slowest rank's clients), not for the next round's training queued behind it
-                # (+ one row per rank — its first slot — so every rank's decision word is checked, also a rank
-                # none of whose clients is selected or valid this round)
-                nsel = sel.shape[0]
-                per_rank = allb[0::block.shape[0], P:P + META + self.E] if block.shape[0] else allb[:0, P:P + META + self.E]
-                mread = self._meta_read(torch.cat([sel[:, P:P + META + self.E], per_rank], 0))
-                # FedAvg / hyper: the aggregate and the next launch go in on the device before the host read
-                esl = self._early_launch(st, last, U=U, sel=sel)
-                mall = mread()
-                meta, rank_rows = mall[:nsel], mall[nsel:]
-                self.comm.check()
-                self._check_decisions(meta.numpy(), rank_rows.numpy()[:, DECISION])
-                if self._pending is not None:
-                    self._pending.result()  # the training has finished by now: surfaces hand-off timeouts
-            if self.phase_sync:
-                self._sync()
-            trace.pop()
+            U, meta, esl = self._gather(launch, last)
             t2 = time.perf_counter()
             mn = meta.numpy()  # (numpy: a handful of tiny host ops, cheaper than torch CPU tensors)
             results = mn[:, 1] > 0.5
@@ -1011,13 +974,12 @@ class FLEngine:
                 round_ok, info = self._early_outcome(esl, results)
             else:
                 with trace.range("fl/aggregate"):
-                    info = self._aggregate(U, sizes, attackers, round_ok)
+                    info = self._aggregate(U, sizes, attackers, round_ok, launch.prep.fedavg_w)
                     if self.phase_sync:  # per-phase timings only; otherwise validation queues behind it
                         self._sync()
             if info.get("agg_failed"):
                 round_ok = False
             t3 = time.perf_counter()
-        self._round_meta = meta
         # ---- genuine pool for the next START (non-attacker rows stored this round; only attackers read it) ----
         if self._has_attackers and U is not None and esl is None:
             keep = self._store_genuine(U, stored)
@@ -1031,8 +993,7 @@ class FLEngine:
         # trainer occupies a few CUs).  Valid whatever validation decides: a failed round is retried from the
         # same global model with the same client counters, i.e. exactly this launch.  Every rank decides
         # the same (replicated validation), so the ranks' launches and gathers stay in lockstep.
-        vstream = None
-        agg_done = None
+        vstream = agg_done = None
         if esl is not None and self._spec is not None:
             agg_done = esl.agg_done
         elif self._speculative and round_ok and self.rounds_left > 1 and not last:
@@ -1048,10 +1009,49 @@ class FLEngine:
             vstream.wait_event(agg_done)
             vstream.wait_event(self._start_ready)
         with (torch.cuda.stream(vstream) if vstream is not None else contextlib.nullcontext()):
-            rec = self._finish_round(snapshot, info, round_ok, t0, t1, t2, t3)
+            rec = self._finish_round(snapshot, info, round_ok, launch.lw_times, meta, t0, t1, t2, t3)
         if vstream is not None:
             self.ckpt_writer.kick()  # the next launch is already in: copy + write while it trains
         return rec
+
+    def _gather(self, launch: Launch, last: bool):
+        """The general path's exchange: (update rows ``U`` of the selected clients, their host meta, the early
+        launch enqueued on the gathered rows or None)."""
+        trace.push("fl/gather")
+        P, block = self.P, launch.block
+        rows = self._local_rows()
+        idx = self._sel_cache[2]
+        esl = None
+        if self.world == 1:  # every row is local: the host already knows the meta columns
+            meta = torch.from_numpy(launch.prep.meta[rows])
+            if launch.plain:
+                U = self.local_params[:len(rows)]  # the trained models ARE the update rows: no block at all
+            else:
+                U = self.comm.all_gather_rows(block).index_select(0, idx)[:, :P].contiguous()
+        else:
+            allb = self.comm.all_gather_rows(block)                    # [world*slots, W]
+            sel = allb.index_select(0, idx)
+            U = sel[:, :P].contiguous()
+            # the round's ONE host read: every client's [valid, result, size, attacker, decision | losses]; it
+            # is queued BEFORE the early launch and waited for through its own event, so the host waits for
+            # the gather (the slowest rank's clients), not for the next round's training queued behind it
+            # (+ one row per rank — its first slot — so every rank's decision word is checked, also a rank
+            # none of whose clients is selected or valid this round)
+            nsel = sel.shape[0]
+            per_rank = allb[0::block.shape[0], P:P + META + self.E] if block.shape[0] else allb[:0, P:P + META + self.E]
+            mread = self._meta_read(torch.cat([sel[:, P:P + META + self.E], per_rank], 0))
+            # FedAvg / hyper: the aggregate and the next launch go in on the device before the host read
+            esl = self._early_launch(launch, last, U=U, sel=sel)
+            mall = mread()
+            meta, rank_rows = mall[:nsel], mall[nsel:]
+            self.comm.check()
+            self._check_decisions(meta.numpy(), rank_rows.numpy()[:, DECISION])
+            if launch.pending is not None:
+                launch.pending.result()  # the training has finished by now: surfaces hand-off timeouts
+        if self.phase_sync:
+            self._sync()
+        trace.pop()
+        return U, meta, esl
 
     def _meta_read(self, cols: torch.Tensor):
         """Start the device -> host copy of the gathered meta columns; returns a callable that waits for THAT
@@ -1059,7 +1059,7 @@ class FLEngine:
         if cols.device.type != "cuda":
             m = cols.double().cpu()
             return lambda: m
-        buf = getattr(self, "_meta_pinned", None)
+        buf = self._meta_pinned
         if buf is None or buf.shape != cols.shape:
             buf = self._meta_pinned = torch.empty(cols.shape, dtype=torch.float32, pin_memory=True)
         buf.copy_(cols, non_blocking=True)
@@ -1096,7 +1096,6 @@ class FLEngine:
         queued beside it on another stream starts before it ends."""
         if self.device.type != "cuda" or getattr(self.trainer, "kind", "") != "graph" or self.model_name != "CNNModel":
             return False
-        from .. import ops
         from ..parallel.launcher import gpu_sharers
 
         cus = torch.cuda.get_device_properties(self.device).multi_processor_count // gpu_sharers()
@@ -1127,7 +1126,7 @@ class FLEngine:
         self.genuine_pool = self._take_rows(U, keep) if keep else None
         return keep
 
-    def _early_launch(self, st: dict, last: bool, U: Optional[torch.Tensor] = None,
+    def _early_launch(self, launch: Launch, last: bool, U: Optional[torch.Tensor] = None,
                       sel: Optional[torch.Tensor] = None) -> Optional["EarlyLaunch"]:
         """This round's server step and the NEXT round's launch, enqueued before the host waits for this round's
         training (one rank, plain rows) or reads the gathered meta (several ranks), so no host work separates two
@@ -1137,34 +1136,34 @@ class FLEngine:
         genuine sample then comes from the stored prefix.  Returns None where the ordinary path runs."""
         if not self._early_ok(last):
             return None
-        if sel is None:  # one rank, plain rows: called before _finish_local
-            if not (self.world == 1 and st.get("plain") and st.get("fedavg_w") is not None):
+        if sel is None:  # one rank, plain rows: before the host waits for the training
+            prep = launch.prep
+            if not (self.world == 1 and launch.plain and prep.fedavg_w is not None):
                 return None
-            self._finish_attacks(st)
-            if not all(ok for _, ok, _ in st["atk_out"]):
+            self._finish_attacks(launch)
+            if not all(ok for _, ok, _ in launch.atk_out):
                 return None
             n = len(self.selected)
             U = self.local_params[:n]
-            ok_all = st["pending"].ok_device()[:n]
+            ok_all = launch.pending.ok_device()[:n]
             if not (self.mode == "fedavg" and ok_all.dtype == torch.int32):  # (FedAvg: reduced inside the aggregate)
                 ok_all = (ok_all > 0).all()
-            w = st["fedavg_w"]
-            sizes = st["sizes_h"]
-            attackers = torch.from_numpy(st["meta"][self._local_rows(), 3] > 0.5)
+            w, sizes = prep.fedavg_w, prep.sizes_h
+            attackers = torch.from_numpy(prep.meta[self._local_rows(), 3] > 0.5)
         else:  # several ranks: called on the gathered rows (device), before the host reads their meta
             P = self.P
             ok_all = ((sel[:, P] > 0.5) & (sel[:, P + 1] > 0.5)).all()
             sizes = sel[:, P + 2].double()
             w = sizes / sizes.sum()
             attackers = sel[:, P + 3] > 0.5
-        # (the next launch's host half was staged ahead: the snapshot already includes its draws, and its clients'
-        # START models come out of the hypernetwork update's last launches)
+        # (the snapshot already includes the staged host half's draws; its clients' START models come out of the
+        # hypernetwork update's last launches)
         esl = EarlyLaunch(g_old=self.global_params, fl_old=self.fltrust_model,
                           hyper_step=self.hyper.step if self.mode == "hyper" else None,
                           snap=([(lc.rng.getstate(), lc.training_round, lc.genuine) for lc in self.local],
                                 self.server_rng.getstate()),
                           prep=self._next_prep)
-        gen_key = [i for _, i, _, _ in esl.prep["clients"]] if esl.prep and esl.prep.get("clients") else None
+        gen_key = [i for _, i, _, _ in esl.prep.clients] if esl.prep is not None and esl.prep.clients else None
         esl.info, rule_ok = self._server_step(U, sizes, attackers, ok_all, w=w, gen_key=gen_key)
         if rule_ok is not None:
             # gmm's success (some row kept): the host reads it after its wait from a pinned copy queued BEFORE the
@@ -1223,16 +1222,16 @@ class FLEngine:
         self._next_prep = esl.prep  # the launch's host half is reused as it was (same draws)
         self.genuine_pool = esl.pool[:m] if m else None
 
-    def _client_losses(self) -> Optional[List[Optional[List[float]]]]:
+    def _client_losses(self, meta: Optional[torch.Tensor]) -> Optional[List[Optional[List[float]]]]:
         """Per-epoch training loss of every selected client (None for attackers and failed clients), from
         the round's meta rows (host mirror on one rank, the gathered block's loss columns otherwise)."""
-        meta = getattr(self, "_round_meta", None)
         if meta is None or meta.shape[1] < META + self.E:
             return None
         return [None if (meta[r, 3] > 0.5 or meta[r, 1] < 0.5)
                 else [round(float(x), 6) for x in meta[r, META:META + self.E]] for r in range(len(self.selected))]
 
-    def _finish_round(self, snapshot, info, round_ok, t0, t1, t2, t3) -> dict:
+    def _finish_round(self, snapshot, info, round_ok, lw_times: Dict[str, float], meta: Optional[torch.Tensor],
+                      t0, t1, t2, t3) -> dict:
         trace.push("fl/validate")
         # ---- replicated detection + validation: every rank computes the same decision ----
         removed: List[int] = []
@@ -1261,7 +1260,7 @@ class FLEngine:
                 else:
                     round_ok, metric = self.validation.test(self.global_params)
         trace.pop()
-        fl_pending, self._fl_pending = getattr(self, "_fl_pending", None), None
+        fl_pending, self._fl_pending = self._fl_pending, None
         if fl_pending is not None:
             fl_pending.result()  # (FLTrust's root training: finished by now; raises on a hand-off timeout)
         t4 = time.perf_counter()
@@ -1276,7 +1275,7 @@ class FLEngine:
         elif self.verbose:
             print_with_color("Training failed!", "yellow")
         t5 = time.perf_counter()
-        rec = {"round": self.round_no, "ok": round_ok, "metric": metric, **getattr(self, "_lw_times", {}),
+        rec = {"round": self.round_no, "ok": round_ok, "metric": metric, **lw_times,
                "t_local": t1 - t0, "t_gather": t2 - t1,
                "t_aggregate": t3 - t2, "t_validate": t4 - t3, "t_checkpoint": t5 - t4, "t_round": t5 - t0,
                "n_selected": len(self.selected), "removed": removed}
@@ -1290,34 +1289,34 @@ class FLEngine:
         if self._trust is not None:
             info["trust"] = [round(float(x), 6) for x in self._trust.tolist()]
         rec.update({k: v for k, v in info.items() if isinstance(v, (int, float, list, str))})
-        losses = self._client_losses()
+        losses = self._client_losses(meta)
         if losses is not None:
             rec["client_loss"] = losses
             if self.verbose:
-                self._print_losses(losses)
+                self._print_losses(losses, meta)
         self.metrics.write(rec)
         self.history.append(rec)
         if round_ok:
             self.round_no += 1
         return rec
 
-    def _print_losses(self, losses) -> None:
+    def _print_losses(self, losses, meta: torch.Tensor) -> None:
         """Reference client prints (``client.py:109`` ICU: ``Loss {mean}`` per epoch; ``client.py:130`` HAR:
         ``Epoch {e}, Loss: {sum:.4f}``), one block per client, from the server's view of the round."""
         for i, ls in zip(self.selected, losses):
             if ls is None:
                 continue
             if self.data_name == "HAR":
-                nb = max(1, -(-int(self._round_meta[self.selected.index(i), 2]) // self.cfg.batch_size))
+                nb = max(1, -(-int(meta[self.selected.index(i), 2]) // self.cfg.batch_size))
                 for e, l in enumerate(ls):
                     print(f"[client {i}] Epoch {e + 1}, Loss: {l * nb:.4f}")
             else:
                 for l in ls:
                     print_with_color(f"[client {i}] Loss {l} ", "yellow")
 
-    def _fedavg_allreduce(self, block: torch.Tensor):
+    def _fedavg_allreduce(self, block: torch.Tensor, meta_host: np.ndarray):
         """FedAvg over one all_reduce: [sum s_i w_i | sum s_i | #failed | #reported] (fp64).  Returns
-        (round ok, host meta of this rank's rows); sets ``global_params`` on success."""
+        (round ok, host meta of the selected rows — one rank only); sets ``global_params`` on success."""
         P = self.P
         present = block[:, P] > 0.5
         size = torch.where(present, block[:, P + 2], torch.zeros_like(block[:, P + 2])).double()
@@ -1343,7 +1342,7 @@ class FLEngine:
         if round_ok:
             self.global_params = (red[:P] / red[P]).to(torch.float32)
         # per-client meta (losses for the JSONL): only a single rank knows every row without another read
-        meta = torch.from_numpy(self._meta_host[self._local_rows()]) if self.world == 1 else None
+        meta = torch.from_numpy(meta_host[self._local_rows()]) if self.world == 1 else None
         return round_ok, meta
 
     def _slot_of(self, i: int) -> int:
@@ -1370,16 +1369,16 @@ class FLEngine:
         return self.history
 
     def close(self):
-        if getattr(self, "_closed", False):
+        if self._closed:
             return
         self._closed = True
         if self._spec is not None:
             # a speculative launch nobody consumed (bench.py drives run_round itself): wait for the GPU work,
             # skip the block / meta bookkeeping.  Client state (local_params, training_round, client RNGs) is
             # then one round ahead of history / round_no.
-            st, self._spec = self._spec, None
-            if st["pending"] is not None:
-                st["pending"].result()
+            launch, self._spec = self._spec, None
+            if launch.pending is not None:
+                launch.pending.result()
             self._sync()
         self.ckpt_writer.close()
         self.metrics.close()

@@ -293,6 +293,28 @@ def _nd(plan: Plan):
     return plan.nd_dev if plan.nd_dev is not None else plan.nd
 
 
+class _ResultRing:
+    """A trainer's pinned [C, 1 + E] result buffers, a ring of 3 (a launch's result is read before the launch
+    after next is enqueued: at most two are in flight)."""
+
+    def __init__(self):
+        self._bufs: List[torch.Tensor] = []
+        self._k = 0
+
+    def read_back(self, ok: torch.Tensor, losses: torch.Tensor, stream) -> Tuple[torch.Tensor, "torch.cuda.Event"]:
+        """Enqueue ONE asynchronous copy of [ok | losses] on ``stream``; returns (the buffer, the copy's event)."""
+        C, E = losses.shape
+        if not self._bufs or self._bufs[0].shape != (C, 1 + E):
+            self._bufs = [torch.empty(C, 1 + E, dtype=torch.float32, pin_memory=True) for _ in range(3)]
+        self._k = (self._k + 1) % len(self._bufs)
+        buf = self._bufs[self._k]
+        with torch.cuda.stream(stream):
+            buf.copy_(torch.cat([ok.to(torch.float32)[:, None], losses], 1), non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(stream)
+        return buf, done
+
+
 class FusedTrainer:
     """All local clients' local rounds in one persistent HIP launch: TransformerModel/ICU
     (``ops/transformer.py``) and RNNModel/ICU (``ops/rnn.py``, falls back to the graph trainer when
@@ -316,6 +338,7 @@ class FusedTrainer:
         self.layout = ParamLayout.for_model(model_name)
         self.verbose = verbose
         self._fallback = None
+        self._ring = _ResultRing()
 
     def train(self, params: torch.Tensor, plan: Plan, lr: float, batch: int, seeds: Sequence[int]
               ) -> Tuple[List[bool], torch.Tensor]:
@@ -343,9 +366,7 @@ class FusedTrainer:
 
         # ok + losses come back in ONE asynchronous copy into a pinned buffer, and result() waits on an event
         # (two blocking .cpu() reads cost two host round trips between the round's training and its aggregate)
-        C, E = losses.shape
-        buf = self._pinned(C, E)
-        done = self._readback(ok, losses, buf)
+        buf, done = self._readback(ok, losses)
 
         def fin():
             # poll instead of a blocking wait: the host then wakes within microseconds of the launch's end
@@ -359,12 +380,12 @@ class FusedTrainer:
 
         return Pending(fin, ok, losses)
 
-    def _readback(self, ok: torch.Tensor, losses: torch.Tensor, buf: torch.Tensor) -> torch.cuda.Event:
-        """Enqueue the result copy; returns its event.  When the launch leaves most CUs free (the on-chip trainers
-        at a few clients per rank) the copy goes on a read-back stream that waits for the training: the compute
-        stream then runs the round's aggregate and the next launch right away instead of three small kernels
-        later.  A launch that fills the GPU keeps the copy on the compute stream (on another stream the copy
-        could wait behind the NEXT launch's persistent workgroups)."""
+    def _readback(self, ok: torch.Tensor, losses: torch.Tensor):
+        """Enqueue the result copy; returns (its pinned buffer, its event).  When the launch leaves most CUs free
+        (the on-chip trainers at a few clients per rank) the copy goes on a read-back stream that waits for the
+        training: the compute stream then runs the round's aggregate and the next launch right away instead of
+        three small kernels later.  A launch that fills the GPU keeps the copy on the compute stream (on another
+        stream the copy could wait behind the NEXT launch's persistent workgroups)."""
         dev = self.device
         main = torch.cuda.current_stream(dev)
         cus = torch.cuda.get_device_properties(dev).multi_processor_count
@@ -384,21 +405,7 @@ class FusedTrainer:
             losses.record_stream(rs)
         else:
             rs = main
-        with torch.cuda.stream(rs):
-            buf.copy_(torch.cat([ok.to(torch.float32)[:, None], losses], 1), non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(rs)
-        return done
-
-    def _pinned(self, C: int, E: int) -> torch.Tensor:
-        """Pinned [C, 1 + E] result buffers, a ring of 3 (a launch's result is read before the launch after
-        next is enqueued: at most two are in flight)."""
-        ring = getattr(self, "_pin_ring", None)
-        if ring is None or ring[0][0].shape != (C, 1 + E):
-            ring = self._pin_ring = ([torch.empty(C, 1 + E, dtype=torch.float32, pin_memory=True) for _ in range(3)], [0])
-        bufs, k = ring
-        k[0] = (k[0] + 1) % len(bufs)
-        return bufs[k[0]]
+        return self._ring.read_back(ok, losses, rs)
 
 
 class OracleTrainer:
@@ -449,6 +456,7 @@ class GraphTrainer:
         self.layout = ParamLayout.for_model(model_name)
         self.verbose = verbose
         self._runner = None
+        self._ring = _ResultRing()
         self.compat_har = False  # engine.compat-har-train (HAR data only)
 
     def train(self, params: torch.Tensor, plan: Plan, lr: float, batch: int, seeds: Sequence[int]
@@ -468,11 +476,7 @@ class GraphTrainer:
             # this launch, and fin() waits on its event: a .cpu() read in fin() went on the stream BEHIND the
             # speculative next launch enqueued meanwhile, so the host waited for that whole training too and
             # enqueued the round after it late (cnn2, which fills the GPU: ~1-2 ms idle per round)
-            C, E = losses.shape
-            buf = FusedTrainer._pinned(self, C, E)
-            buf.copy_(torch.cat([ok.to(torch.float32)[:, None], losses], 1), non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(torch.cuda.current_stream(self.device))
+            buf, done = self._ring.read_back(ok, losses, torch.cuda.current_stream(self.device))
 
             def host():
                 while not done.query():

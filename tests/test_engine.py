@@ -423,3 +423,64 @@ def test_decision_check_covers_ranks_without_selected_clients():
     mn[1, 0] = 0.0  # an invalid row's word is ignored, the per-rank words are not
     mn[1, DECISION] = 5.0
     FLEngine._check_decisions(stub, mn, np.array([77.0, 77.0]))
+
+
+def _one_round(tmp_path, name, selected=None):
+    """One fedavg round of a fresh engine: (engine, record, local_params before the round, the selected clients'
+    sizes as each client's RNG draws them)."""
+    import random
+
+    eng = FLEngine(from_dict(_cfg(tmp_path / name, server__num_round=1)), device="cpu", verbose=False)
+    eng.client_selection()
+    if selected is not None:
+        eng.selected = list(selected)
+    before = eng.local_params.clone()
+    sizes = []
+    for lc in eng.local:
+        if lc.info.index in eng.selected:
+            r = random.Random()
+            r.setstate(lc.rng.getstate())
+            sizes.append(r.randrange(150, 260 + 1))
+    rec = eng.run_round()
+    eng.close()
+    return eng, rec, before, sizes
+
+
+def test_subset_of_local_clients_trains_through_the_scatter_path(tmp_path):
+    """Three of four local clients selected: the launch gathers their rows, trains them and scatters them back
+    (not in place).  A client's draws, plan and dropout seed do not depend on who else is selected, so its trained
+    model and losses equal those of the round with all four; the unselected model stays untouched; FedAvg is the
+    fp64 size-weighted mean of the three rows within 4 fp32 ulp of max|U|."""
+    import numpy as np
+
+    a, rec_a, before_a, _ = _one_round(tmp_path, "a")
+    b, rec_b, before_b, sizes = _one_round(tmp_path, "b", selected=[0, 1, 3])
+    assert rec_a["ok"] and rec_b["ok"]
+    assert rec_b["n_selected"] == 3 and len(rec_b["client_loss"]) == 3
+    for r in (0, 1, 3):
+        assert torch.equal(a.local_params[r], b.local_params[r]), r
+    assert torch.equal(b.local_params[2], before_b[2])
+    assert torch.equal(before_a[2], before_b[2]) and not torch.equal(a.local_params[2], before_a[2])
+    assert rec_b["client_loss"] == [rec_a["client_loss"][r] for r in (0, 1, 3)]
+    U = b.local_params[[0, 1, 3]].double()
+    s = torch.tensor(sizes, dtype=torch.float64)
+    assert len(sizes) == 3 and all(150 <= x <= 260 for x in sizes)
+    want = (s[:, None] * U).sum(0) / s.sum()
+    err = float((b.global_params.double() - want).abs().max())
+    bound = 4 * float(np.spacing(np.float32(U.abs().max())))
+    print(f"fedavg |got - fp64 mean| = {err:.3e}, bound {bound:.3e}")
+    assert err <= bound
+
+
+def test_round_record_keys_are_stable(tmp_path):
+    """The round record's keys are an interface (bench.py and the A/B tooling read them)."""
+    import math
+
+    _, rec, _, _ = _one_round(tmp_path, "k")
+    want = {"round", "ok", "metric", "t_lw_prep", "t_lw_prep_host", "t_lw_prep_upload", "t_lw_launch", "t_lw_attack",
+            "t_lw_wait", "t_lw_post", "t_local", "t_gather", "t_aggregate", "t_validate", "t_checkpoint", "t_round",
+            "n_selected", "removed", "client_loss"}
+    assert want <= set(rec), want - set(rec)
+    for k, v in rec.items():
+        if k.startswith("t_"):
+            assert isinstance(v, float) and math.isfinite(v) and v >= 0.0, (k, v)
