@@ -28,6 +28,11 @@ front (6 for γ0 = 50, τ = 1) and only the path depends on the data.  ``_bisect
 unrolls the loop with γ, γ_succ and every accept decision as device scalars (``torch.where``
 updates): no host synchronisation per γ — the whole attack is enqueued on the attacker's side stream
 and its γ reaches the host only when the round's record is written.
+
+**AGR-tailored attacks (beyond the reference).**  ``AGR-Krum`` / ``AGR-MKrum`` / ``AGR-Bulyan`` (``agr_tailored``) run
+the same bisection schedule, but their acceptance test is the selection rule itself on the K genuine rows plus m copies
+of the candidate (``ops.composite.agr_oracle``, ``k_agr_bisect`` on the device), and they return the last ACCEPTED
+candidate.  Definition in docs/PARITY.md.
 """
 from __future__ import annotations
 
@@ -36,6 +41,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
+from ..config import AGR_ATTACK_TARGETS, agr_attack_args
 from ..models import ParamLayout
 from ..utils.log import print_with_color
 from .. import ops
@@ -303,6 +309,33 @@ def opt_fang(G, own, engine, **kw) -> AttackResult:
     return _minmax_family(G, own, engine, "fang", **kw)
 
 
+def agr_tailored(G: torch.Tensor, own: torch.Tensor, mode: str, args: Sequence[float] = (), gamma: float = 10.0,
+                 tau: float = 0.02) -> AttackResult:
+    """The AGR-tailored attacks on Krum / Multi-Krum / Bulyan (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 1;
+    definition in docs/PARITY.md): the largest γ on the bisection's schedule at which the rule, run on the K genuine
+    rows plus m identical copies of c(γ) = mean - γ·dev (the copies last, squared flat L2 distances whatever
+    ``engine.distance`` says), still selects the copies.  ``args = [m, f, dev]`` (``config.agr_attack_args``).  The
+    result is c(γ_succ) with γ_succ the last ACCEPTED γ (the mean when none was); nothing is written into ``G[0]`` (A-7
+    does not apply).  K <= 1, or a system the rule does not admit (n' = K + m < 2f + 3, Bulyan 4f + 3), returns the
+    attacker's own model.  Closed form: one pass over ``[K, P]`` for A, B, C and the genuine distances, then the
+    whole bisection in one launch (``k_agr_bisect``) on the device, with no host read."""
+    target = AGR_ATTACK_TARGETS[mode]
+    m, f, kind = agr_attack_args(mode, args)
+    K = G.shape[0]
+    meta = {"m": m, "f": f, "target": target}
+    if K <= 1 or not ops.composite.agr_admissible(K + m, f, target):
+        return AttackResult(True, own.clone(), {"gamma": 0.0, "iters": 0, **meta})
+    st = column_stats(G)
+    dev = (st.std, st.sign, None)[kind]
+    if dev is None:
+        dev = st.mean / torch.linalg.vector_norm(st.mean)
+    A, B, C = ops.attack_coeffs(G, st.mean, dev)
+    last, iters, succ, tried, accs = ops.agr_bisect(ops.pairwise_sqdist(G), A, B, C, m, f, target, gamma, tau)
+    mal = st.mean - succ * dev
+    return AttackResult(True, mal, {"gamma": succ, "gamma_succ": succ, "iters": iters, "gammas": tried,
+                                    "accepted": accs, **meta})
+
+
 def lie(G: torch.Tensor, own: torch.Tensor, engine: DistanceEngine = None, scaling_factor: float = 0.74) -> AttackResult:
     """Little-Is-Enough: mean + z·std (reference ``create_LIE_state_dict``)."""
     return AttackResult(True, ops.lie_candidate(G, float(scaling_factor)), {"z": float(scaling_factor)})
@@ -315,9 +348,13 @@ def random_noise(own: torch.Tensor, perturbation: float, seed: int = 0) -> Attac
 
 
 def run_attack(mode: str, args: Sequence[float], own: torch.Tensor, G: Optional[torch.Tensor], engine: DistanceEngine,
-               seed: int = 0, gamma: float = 50.0, tau: float = 1.0) -> AttackResult:
-    """Dispatch by the reference's ``--attack_mode`` names.  ``seed`` keys the Random attack's noise;
-    ``gamma`` / ``tau`` start and stop the bisection attacks (reference: fixed 50 / 1)."""
+               seed: int = 0, gamma: Optional[float] = None, tau: Optional[float] = None) -> AttackResult:
+    """Dispatch by the reference's ``--attack_mode`` names plus the AGR-tailored modes.  ``seed`` keys the Random
+    attack's noise; ``gamma`` / ``tau`` start and stop the bisection attacks (unset: the reference's fixed 50 / 1,
+    and 10 / 0.02 for the AGR-tailored modes, as ``config.AttackSpec``)."""
+    agr = mode in AGR_ATTACK_TARGETS
+    gamma = float((10.0 if agr else 50.0) if gamma is None else gamma)
+    tau = float((0.02 if agr else 1.0) if tau is None else tau)
     if mode == "Random":
         sigma = args[0] if args else 1e6
         return random_noise(own, sigma, seed)
@@ -329,6 +366,8 @@ def run_attack(mode: str, args: Sequence[float], own: torch.Tensor, G: Optional[
         return min_sum(G, own, engine, gamma=gamma, tau=tau)
     if mode == "Opt-Fang":
         return opt_fang(G, own, engine, gamma=gamma, tau=tau)
+    if agr:
+        return agr_tailored(G, own, mode, args, gamma=gamma, tau=tau)
     if mode == "LIE":
         z = args[0] if args else 0.74
         if G.shape[0] == 1:
@@ -338,4 +377,4 @@ def run_attack(mode: str, args: Sequence[float], own: torch.Tensor, G: Optional[
     raise ValueError(f"Attack client not contain '{mode}' algorithm.")
 
 
-ATTACKS = ("Random", "Min-Max", "Min-Sum", "Opt-Fang", "LIE")
+ATTACKS = ("Random", "Min-Max", "Min-Sum", "Opt-Fang", "LIE", "AGR-Krum", "AGR-MKrum", "AGR-Bulyan")

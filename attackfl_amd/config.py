@@ -16,7 +16,10 @@ Extensions (all optional, defaults keep reference behaviour):
                             [sum s_i w_i | sum s_i] instead of the update all-gather; auto = world > 1
                             without the IPC path)
   timeout-s: collective timeout (failure detection)
-  attackers: {client_index: {mode, round, args}}  (launcher-side attack assignment)
+  attackers: {client_index: {mode, round, args, gamma, tau}}  (launcher-side attack assignment; mode: the
+                            reference's Random | LIE | Min-Max | Min-Sum | Opt-Fang plus the AGR-tailored AGR-Krum |
+                            AGR-MKrum | AGR-Bulyan with args [m, f, dev], docs/PARITY.md; gamma / tau: the bisection's
+                            start and stop gap, default 50 / 1, for the AGR modes 10 / 0.02)
 ``data:``
   synthetic: auto | true | false   (auto = use the reference pickles when present)
   train-size / test-size / seed / har-train-size / har-test-size
@@ -71,7 +74,30 @@ import yaml
 
 SERVER_MODES = ("fedavg", "hyper", "FLTrust", "trimmed_mean", "shieldfl", "gmm", "krum", "median", "scionfl",
                 "fltracer", "byzantine", "multi_krum", "bulyan", "geomed", "dnc")
-ATTACK_MODES = ("Random", "Min-Max", "Min-Sum", "Opt-Fang", "LIE")
+ATTACK_MODES = ("Random", "Min-Max", "Min-Sum", "Opt-Fang", "LIE", "AGR-Krum", "AGR-MKrum", "AGR-Bulyan")
+# the AGR-tailored attacks (beyond the reference; docs/PARITY.md) and the rule each one models
+AGR_ATTACK_TARGETS = {"AGR-Krum": "krum", "AGR-MKrum": "mkrum", "AGR-Bulyan": "bulyan"}
+
+
+def agr_attack_args(mode: str, args) -> tuple:
+    """``attack_args = [m, f, dev]`` of an AGR-tailored attack, all optional -> (m, f, dev) as ints: m >= 1 identical
+    malicious copies the attacker assumes (default 1), f the Byzantine count it assumes the rule runs with (default m;
+    f = 0, this project's ``server.mode: krum`` (A-11), only for AGR-Krum), dev 0 = unbiased std, 1 = sign(mean),
+    2 = mean / ||mean||_2.  A non-integer or out-of-range value raises ValueError."""
+    vals = [float(a) for a in (args or [])]
+    if len(vals) > 3:
+        raise ValueError(f"{mode} takes at most 3 attack args [m, f, dev] (got {vals})")
+    for name, v in zip(("m", "f", "dev"), vals):
+        if v != v or v != int(v):
+            raise ValueError(f"{mode}: attack arg {name} must be an integer (got {v})")
+    m = int(vals[0]) if len(vals) > 0 else 1
+    f = int(vals[1]) if len(vals) > 1 else m
+    dev = int(vals[2]) if len(vals) > 2 else 0
+    fmin = 0 if mode == "AGR-Krum" else 1
+    if m < 1 or f < fmin or dev not in (0, 1, 2):
+        raise ValueError(f"{mode}: attack args [m, f, dev] need m >= 1, f >= {fmin} and dev in 0 / 1 / 2 "
+                         f"(got m = {m}, f = {f}, dev = {dev})")
+    return m, f, dev
 MODEL_NAMES = ("CNNModel", "RNNModel", "TransformerModel", "TransformerClassifier")
 DATA_NAMES = ("ICU", "HAR", "CIFAR10")
 
@@ -126,19 +152,27 @@ class AttackSpec:
     """One attacker's schedule.  ``gamma`` / ``tau`` are the Min-Max / Min-Sum / Opt-Fang bisection's start
     value and stop gap; the reference hard-codes them to 50 and 1 (``src/Utils.py:101,134,167``), which
     stay the defaults.  With those the tried γs are 50, 25, ..., 1.5625 and a candidate can only be
-    accepted at γ ≥ 1.5625 (profiles/attack_study/README.md shows why that rarely passes the distance check)."""
+    accepted at γ ≥ 1.5625 (profiles/attack_study/README.md shows why that rarely passes the distance check).
+    Left unset (None) they resolve to those 50 / 1 for the reference's five modes and to 10 / 0.02 for the AGR-tailored
+    modes (10 is the start value of the NDSS 2021 paper's published code; 9 iterations, γ resolved to 0.04): a
+    candidate that a Krum-type rule still selects sits at γ of about 1, below anything 50 / 1 can accept.  The AGR
+    modes' ``args`` are ``[m, f, dev]`` (``agr_attack_args``), checked here, not at round ``round``."""
     mode: str
     round: int
     args: List[float] = field(default_factory=list)
-    gamma: float = 50.0
-    tau: float = 1.0
+    gamma: Optional[float] = None
+    tau: Optional[float] = None
 
     def __post_init__(self):
         if self.mode not in ATTACK_MODES:
             raise ValueError(f"Attack mode '{self.mode}' is not valid (choose from {ATTACK_MODES}).")
         self.round = int(self.round)
         self.args = [float(a) for a in (self.args or [])]
-        self.gamma, self.tau = float(self.gamma), float(self.tau)
+        agr = self.mode in AGR_ATTACK_TARGETS
+        if agr:
+            agr_attack_args(self.mode, self.args)
+        self.gamma = float((10.0 if agr else 50.0) if self.gamma is None else self.gamma)
+        self.tau = float((0.02 if agr else 1.0) if self.tau is None else self.tau)
         if not (self.gamma > 0 and self.tau > 0):
             raise ValueError(f"bisection gamma / tau must be positive (got {self.gamma}, {self.tau})")
 
@@ -147,7 +181,7 @@ class AttackSpec:
 
     @classmethod
     def from_dict(cls, v: Dict[str, Any]) -> "AttackSpec":
-        return cls(v["mode"], v.get("round", 1), v.get("args", []), v.get("gamma", 50.0), v.get("tau", 1.0))
+        return cls(v["mode"], v.get("round", 1), v.get("args", []), v.get("gamma"), v.get("tau"))
 
 
 @dataclass

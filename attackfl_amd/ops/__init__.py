@@ -311,6 +311,36 @@ def krum_select(D: torch.Tensor, f: int, rounds: int, iterated: bool):
     return composite.krum_select(D, int(f), int(rounds), bool(iterated))
 
 
+def agr_bisect_fused(Dg: torch.Tensor, A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, m: int, f: int, target: str,
+                     n_iter: int, gamma: float) -> Optional[torch.Tensor]:
+    """The AGR-tailored bisection as ONE launch (``agg.hip`` ``k_agr_bisect``) -> the state ``st [40]`` fp64 (st[1] last
+    accepted γ, st[2] last tried, st[4 + i] tried, st[20 + i] accepted), or None where the kernel does not apply (CPU
+    tensors, n' = K + m > 64, more than 16 iterations or none).  No host read and no pageable scalar copy."""
+    if not _dev(Dg) or Dg.shape[0] + m > 64 or not 1 <= n_iter <= 16:
+        return None
+    f64 = lambda t: t.to(device=Dg.device, dtype=torch.float64).contiguous()
+    st = torch.zeros(40, dtype=torch.float64, device=Dg.device)
+    st[:1].fill_(float(gamma))  # (st[0] = x is a pageable scalar copy: a host wait for the side stream)
+    native().agr_bisect(st, f64(Dg), f64(A).reshape(-1), f64(B).reshape(-1), f64(C).reshape(1), int(m), int(f),
+                        composite.AGR_TARGETS.index(target), int(n_iter), float(gamma))
+    return st
+
+
+def agr_bisect(Dg: torch.Tensor, A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, m: int, f: int, target: str,
+               gamma: float, tau: float):
+    """Bisection on γ with the oracle "the rule ``target`` still selects the m copies of mean - γ·dev"
+    (``composite.agr_oracle``) -> (last tried γ, iterations, last accepted γ, tried γs [n], decisions [n]) with the γs as
+    fp64 tensors on the inputs' device.  Device, n' <= 64: ``k_agr_bisect``; otherwise the unrolled loop with
+    device-side state (``attacks._bisect_device``) over the composite.  Neither reads a value back."""
+    from ..attacks import _bisect_device, bisect_iterations
+
+    n = bisect_iterations(gamma, tau)
+    st = agr_bisect_fused(Dg, A, B, C, m, f, target, n, gamma)
+    if st is not None:
+        return st[2], n, st[1], st[4:4 + n], st[20:20 + n] > 0.5
+    return _bisect_device(lambda g: composite.agr_oracle(Dg, A, B, C, g, m, f, target), gamma, tau, Dg.device)
+
+
 def bulyan_coord(U: torch.Tensor, sel: torch.Tensor, beta: int) -> torch.Tensor:
     """Per column, the mean of the ``beta`` values closest to the lower median over the rows ``sel`` of U (a device
     index list on the device path: ``k_bulyan_coord`` reads the selected rows in place)."""

@@ -156,6 +156,92 @@ def krum_select(D: torch.Tensor, f: int, rounds: int, iterated: bool):
     return torch.stack(sel), ~active, first
 
 
+AGR_TARGETS = ("krum", "mkrum", "bulyan")  # (the kernel's target 0 / 1 / 2)
+
+
+def agr_admissible(n: int, f: int, target: str) -> bool:
+    """Whether the rule ``target`` runs on n rows with f assumed Byzantine ones: n >= 2 f + 3 (Krum, Multi-Krum),
+    n >= 4 f + 3 (Bulyan)."""
+    return f >= 0 and n >= (4 * f + 3 if target == "bulyan" else 2 * f + 3)
+
+
+def agr_rounds(n: int, f: int, target: str):
+    """(rounds, iterated) of ``krum_select`` for the rule: Krum 1 pick, Multi-Krum n - f picks of one ranking, Bulyan
+    n - 2 f picks re-scored every time."""
+    return {"krum": (1, False), "mkrum": (n - f, False), "bulyan": (n - 2 * f, True)}[target]
+
+
+def agr_matrix(Dg: torch.Tensor, A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, gamma, m: int) -> torch.Tensor:
+    """The modelled system's squared distances [K + m, K + m] fp64: the K genuine rows first (``Dg``, read as
+    symmetric from its upper triangle), then m identical copies of c(γ) = mean - γ·dev at squared distance
+    max(A_j - 2γB_j + γ²C, 0) from genuine row j (``attack_coeffs``) and 0 from each other."""
+    K = Dg.shape[0]
+    Dg = torch.triu(Dg.double(), 1)
+    d = (A.double() - 2.0 * gamma * B.double() + gamma * gamma * C.double()).clamp_min(0.0)
+    D = torch.zeros(K + m, K + m, dtype=torch.float64, device=Dg.device)
+    D[:K, :K] = Dg + Dg.t()
+    D[:K, K:] = d[:, None]
+    D[K:, :K] = d[None, :]
+    return D
+
+
+def agr_oracle(Dg: torch.Tensor, A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, gamma, m: int, f: int,
+               target: str) -> torch.Tensor:
+    """Would the rule still select the attacker's rows at this γ (``agg.hip`` ``k_agr_bisect``)?  ``krum_select`` on
+    ``agr_matrix`` with ``agr_rounds``: Krum accepts when the pick is a copy (index >= K), Multi-Krum and Bulyan when
+    all m copies are selected; a NaN in A, B or C rejects.  The copies hold the last indices, so every index tie goes
+    against the attacker.  -> 0-d bool tensor; tensor ops only (no host read)."""
+    K = Dg.shape[0]
+    rounds, iterated = agr_rounds(K + m, f, target)
+    sel, mask, _ = krum_select(agr_matrix(Dg, A, B, C, gamma, m), f, rounds, iterated)
+    acc = (sel[0] >= K) if target == "krum" else mask[K:].all()
+    nan = torch.isnan(A).any() | torch.isnan(B).any() | torch.isnan(C).any()
+    return acc & ~nan
+
+
+def agr_oracle_margin(Dg: torch.Tensor, A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, gamma, m: int, f: int,
+                      target: str):
+    """``agr_oracle``'s diagnostic twin (host reads; for tests and studies) -> (accept bool, decision margin float).
+    The same picks, written out, with at every pick gap = |score(picked) - the smallest score among the other active
+    rows| / the largest finite first-pass score; when the picked row is a copy the other copies (whose scores are the
+    same bits) are left out of the others.  The margin is the smallest non-zero gap over the picks (inf when there is
+    none): perturbations of the scores below it cannot change a pick.  A zero gap is an exact tie (identical copies,
+    or the k = 1 mutual-nearest tie ``krum_select`` documents) that the index decides the same way on every side."""
+    K = Dg.shape[0]
+    n = K + m
+    rounds, iterated = agr_rounds(n, f, target)
+    D = agr_matrix(Dg, A, B, C, gamma, m).cpu()
+    inf = float("inf")
+    idx = torch.arange(n)
+    eye = idx[:, None] == idx[None, :]
+    active = torch.ones(n, dtype=torch.bool)
+    sel, sc, scale, margin = [], None, 1.0, inf
+    for t in range(rounds):
+        if t == 0 or iterated:
+            k = max((n - t if iterated else n) - f - 2, 1)
+            if iterated and n - t == 1:
+                sc = torch.zeros(n, dtype=torch.float64)
+            else:
+                W = D.masked_fill(eye | ~active[None, :], inf)
+                sc = torch.cumsum(torch.sort(W, dim=1).values, dim=1)[:, k - 1]
+            if t == 0:
+                fin = sc[torch.isfinite(sc)]
+                scale = float(fin.max()) if fin.numel() and float(fin.max()) > 0 else 1.0
+        i = int(torch.argmin(torch.where(active, sc, torch.full_like(sc, inf))))
+        others = active & (idx != i)
+        if i >= K:
+            others = others & (idx < K)
+        if bool(others.any()):
+            gap = abs(float(sc[i]) - float(sc[others].min())) / scale
+            if gap > 0.0:
+                margin = min(margin, gap)
+        sel.append(i)
+        active = active & (idx != i)
+    acc = (sel[0] >= K) if target == "krum" else all(not bool(active[j]) for j in range(K, n))
+    nan = bool(torch.isnan(A).any() | torch.isnan(B).any() | torch.isnan(C).any())
+    return bool(acc) and not nan, margin
+
+
 def bulyan_coord(U: torch.Tensor, sel: torch.Tensor, beta: int) -> torch.Tensor:
     """Bulyan's coordinate step over the rows ``sel`` of U: per column the mean of the ``beta`` values with the
     smallest key (|x - med| in fp32, x), med the lower median (``k_bulyan_coord``)."""

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """FL client — same flags as the reference (reference client.py:19-38):
 
-    python client.py [--device D] [--attack True --attack_mode {Random,Min-Max,Min-Sum,Opt-Fang,LIE}
-                      --attack_round R --attack_args F ...]
+    python client.py [--device D] [--attack True --attack_mode {Random,Min-Max,Min-Sum,Opt-Fang,LIE,
+                      AGR-Krum,AGR-MKrum,AGR-Bulyan} --attack_round R --attack_args F ...]
 
 Registers with the server's rendezvous, receives its client index (registration order r = 1..N), and runs its
 rounds inside the SPMD engine as rank r - 1 of the N-client group, on GPU ``(r - 1) % device_count`` unless
@@ -11,6 +11,9 @@ fused HIP trainer on GPU (eager PyTorch on CPU) or, once ``training_round >= att
 been received, the attack.  Every client rank holds the replicated server state; client 1 (rank 0) is the leader
 that logs ``app.log`` and writes the checkpoints where the server would.
 Unlike the reference (``type=bool``, A-9) ``--attack False`` really disables the attack.
+Beyond the reference's five modes, ``AGR-Krum`` / ``AGR-MKrum`` / ``AGR-Bulyan`` are the AGR-tailored attacks on the
+Krum family (docs/PARITY.md) with ``--attack_args m f dev``: the malicious copies the attacker assumes (default 1), the
+Byzantine count it assumes the rule runs with (default m) and the perturbation (0 std, 1 sign, 2 unit mean).
 """
 from __future__ import annotations
 
@@ -37,8 +40,10 @@ def parse_args(argv=None):
     ap.add_argument("--device", type=str, required=False, help="Device of client")
     ap.add_argument("--attack", type=_bool, required=False, default=False,
                     help="Set to True to enable attack mode, False otherwise.")
-    ap.add_argument("--attack_mode", type=str, choices=["Random", "Min-Max", "Min-Sum", "Opt-Fang", "LIE"],
-                    help="Mode of operation when the attack is enabled (e.g., Random or Min-Max, Min-Sum ...).")
+    ap.add_argument("--attack_mode", type=str,
+                    choices=["Random", "Min-Max", "Min-Sum", "Opt-Fang", "LIE", "AGR-Krum", "AGR-MKrum", "AGR-Bulyan"],
+                    help="Mode of operation when the attack is enabled (e.g., Random or Min-Max, Min-Sum ...; "
+                         "AGR-Krum / AGR-MKrum / AGR-Bulyan: AGR-tailored, --attack_args m f dev).")
     ap.add_argument("--attack_round", type=int, help="Client attack at round.")
     ap.add_argument("--attack_args", type=float, nargs="+", required=False,
                     help="A list of attack args. Use space to separate values (e.g., 0.1 0.2 0.5).")

@@ -185,6 +185,34 @@ std::vector<torch::Tensor> krum_select(torch::Tensor D, int64_t f, int64_t round
   return {sel, mask, scores};
 }
 
+// AGR-tailored bisection (attacks AGR-Krum / AGR-MKrum / AGR-Bulyan): st [40] fp64 with st[0] = gamma0, Dg [K, K],
+// A / B [K], C scalar, all fp64 on one device; the trace lands in st.  Refused here, before any launch, when the
+// modelled system does not fit the kernel or the rule.
+void agr_bisect(torch::Tensor st, torch::Tensor Dg, torch::Tensor A, torch::Tensor B, torch::Tensor C, int64_t m,
+                int64_t f, int64_t target, int64_t n_iter, double gamma0) {
+  check_dev(st, "st", torch::kFloat64);
+  check_dev(Dg, "Dg", torch::kFloat64);
+  check_dev(A, "A", torch::kFloat64);
+  check_dev(B, "B", torch::kFloat64);
+  check_dev(C, "C", torch::kFloat64);
+  const int64_t K = Dg.size(0);
+  TORCH_CHECK(Dg.dim() == 2 && Dg.size(1) == K && K >= 1, "agr_bisect: Dg [K, K], K >= 1");
+  TORCH_CHECK(A.dim() == 1 && A.size(0) == K && B.dim() == 1 && B.size(0) == K && C.numel() == 1,
+              "agr_bisect: A / B [K], C scalar");
+  TORCH_CHECK(st.dim() == 1 && st.numel() >= 40, "agr_bisect: state [40]");
+  for (const torch::Tensor* t : {&Dg, &A, &B, &C})
+    TORCH_CHECK(t->device() == st.device(), "agr_bisect: every tensor on the state's device");
+  TORCH_CHECK(m >= 1 && K + m <= 64, "agr_bisect: n' = K + m = ", K + m, " needs m >= 1 and n' <= 64");
+  TORCH_CHECK(afl_agr_admissible(K + m, f, (int)target) && target == (int)target && f <= 64,
+              "agr_bisect: n' = ", K + m, ", f = ", f, ", target = ", target,
+              " is not admissible (target 0 / 1: f >= 0, n' >= 2 f + 3; 2: n' >= 4 f + 3)");
+  TORCH_CHECK(n_iter >= 1 && n_iter <= 16, "agr_bisect: 1 <= n_iter <= 16 (got ", n_iter, ")");
+  TORCH_CHECK(afl_agr_bisect(Dg.data_ptr<double>(), A.data_ptr<double>(), B.data_ptr<double>(), C.data_ptr<double>(),
+                             (int)K, (int)m, (int)f, (int)target, (int)n_iter, gamma0, st.data_ptr<double>(),
+                             cur()) == 0, "agr_bisect launch failed");
+  AFL_CHECK_LAUNCH();
+}
+
 // Bulyan's coordinate step (agg.bulyan): U [N, P] fp32, sel [theta] int32 (device) -> [P]
 torch::Tensor bulyan_coord(torch::Tensor U, torch::Tensor sel, int64_t beta) {
   check_dev(U, "U", torch::kFloat32);
@@ -905,6 +933,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gmm_filter", &gmm_filter, pybind11::arg("G"), pybind11::arg("att"), pybind11::arg("rank") = 0);
   m.def("top_pc", &top_pc);
   m.def("krum_select", &krum_select);
+  m.def("agr_bisect", &agr_bisect);
   m.def("dnc_run", &dnc_run);
   m.def("bulyan_coord", &bulyan_coord);
   m.def("geomed_weights", &geomed_weights);

@@ -437,6 +437,16 @@ int afl_top_pc(const double* G, int n, int sweeps, double* z, hipStream_t s);
 // Bulyan) -> sel [rounds] int32 in selection order, mask [n] 0/1, scores [n] fp64 of the first pass
 int afl_krum_select(const double* D, int n, int f, int rounds, int iterated, int* sel, unsigned char* mask,
                     double* scores, hipStream_t s);
+// AGR-tailored bisection (agg.hip k_agr_bisect; attacks AGR-Krum / AGR-MKrum / AGR-Bulyan, docs/PARITY.md): K genuine
+// rows with squared distances Dg [K][K] fp64 plus m copies of mean - gamma dev at squared distance
+// max(A_j - 2 gamma B_j + gamma^2 C, 0); target 0 Krum, 1 Multi-Krum, 2 Bulyan with the assumed Byzantine count f; n_iter
+// gammas from st[0] (= gamma0) in ONE launch, trace in st [40] (the bisect_decide layout).  hipErrorInvalidValue
+// unless 1 <= K, 1 <= m, K + m <= 64, f >= 0, K + m >= 2 f + 3 (Bulyan: 4 f + 3) and 1 <= n_iter <= 16.
+inline bool afl_agr_admissible(long n, long f, int target) {
+  return target >= 0 && target <= 2 && f >= 0 && n >= (target == 2 ? 4 * f + 3 : 2 * f + 3);
+}
+int afl_agr_bisect(const double* Dg, const double* A, const double* B, const double* C, int K, int m, int f, int target,
+                   int n_iter, double gamma0, double* st, hipStream_t s);
 // Bulyan's coordinate step over the theta rows sel[] of U [N][P] (agg.hip k_bulyan_coord): per column the mean of the
 // beta values closest to the lower median
 int afl_bulyan_coord(const float* U, int N, long P, const int* sel, int theta, int beta, float* out, hipStream_t s);

@@ -1226,19 +1226,16 @@ int afl_dnc_select(const double* src, int nb, int n, int iters, int centre, int 
 // rows that are each other's nearest neighbour tie EXACTLY, and the tie rule only means something if D[i][j] and
 // D[j][i] are the same bits (a Gram product computed as a full matrix product may differ in the last bit).
 constexpr int KS_LD = GMM_MAXN + 1;
+constexpr int BSA_TRIED = 4, BSA_ACC = 20;  // (the st[40] layout of linalg.hip bisect_decide)
 
-__global__ void __launch_bounds__(64) k_krum_select(const double* __restrict__ D, int n, int f, int rounds, int iterated,
-                                                    int* __restrict__ sel, unsigned char* __restrict__ mask,
-                                                    double* __restrict__ scores) {
-  __shared__ double V[GMM_MAXN * KS_LD];
-  __shared__ unsigned char J[GMM_MAXN * KS_LD];
+// The rule on a matrix already laid out in LDS (V the values, J the column of every entry, row stride KS_LD; the
+// caller has synchronised after filling them): sort, score, pick.  Every trip count is fixed by (n, rounds): no
+// loop depends on a value.  -> the active mask after ``rounds`` picks (wave-uniform), ``first`` = the first pick.
+// ``sel`` / ``scores`` may be null (k_agr_bisect only wants the mask).
+__device__ __forceinline__ unsigned long long krum_select_wave(double* V, unsigned char* J, int n, int f, int rounds,
+                                                               int iterated, int* __restrict__ sel,
+                                                               double* __restrict__ scores, int& first) {
   const int i = threadIdx.x;
-  for (int e = i; e < n * n; e += 64) {
-    const int r = e / n, c = e - r * n;
-    V[r * KS_LD + c] = r <= c ? D[e] : D[c * n + r];  // (the upper triangle, see above)
-    J[r * KS_LD + c] = (unsigned char)c;
-  }
-  __syncthreads();
   if (i < n) {
     double* v = V + i * KS_LD;
     unsigned char* jx = J + i * KS_LD;
@@ -1257,6 +1254,7 @@ __global__ void __launch_bounds__(64) k_krum_select(const double* __restrict__ D
   }
   unsigned long long act = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
   double sc = 0.0;
+  first = 0;
   for (int t = 0; t < rounds; ++t) {
     const bool mine = i < n && ((act >> i) & 1ull);
     if (t == 0 || iterated) {
@@ -1273,7 +1271,7 @@ __global__ void __launch_bounds__(64) k_krum_select(const double* __restrict__ D
           }
         }
       }
-      if (t == 0 && i < n) scores[i] = sc;
+      if (t == 0 && i < n && scores) scores[i] = sc;
     }
     int bi = mine ? i : 64;
     double bs = sc;
@@ -1286,9 +1284,27 @@ __global__ void __launch_bounds__(64) k_krum_select(const double* __restrict__ D
       bi = take ? oi : bi;
     }
     bi = __shfl(bi, 0, 64) & 63;  // (rounds <= n: an active row exists, so the index is one of [0, n))
-    if (i == 0) sel[t] = bi;
+    if (i == 0 && sel) sel[t] = bi;
+    if (t == 0) first = bi;
     act &= ~(1ull << bi);
   }
+  return act;
+}
+
+__global__ void __launch_bounds__(64) k_krum_select(const double* __restrict__ D, int n, int f, int rounds, int iterated,
+                                                    int* __restrict__ sel, unsigned char* __restrict__ mask,
+                                                    double* __restrict__ scores) {
+  __shared__ double V[GMM_MAXN * KS_LD];
+  __shared__ unsigned char J[GMM_MAXN * KS_LD];
+  const int i = threadIdx.x;
+  for (int e = i; e < n * n; e += 64) {
+    const int r = e / n, c = e - r * n;
+    V[r * KS_LD + c] = r <= c ? D[e] : D[c * n + r];  // (the upper triangle, see above)
+    J[r * KS_LD + c] = (unsigned char)c;
+  }
+  __syncthreads();
+  int first;
+  const unsigned long long act = krum_select_wave(V, J, n, f, rounds, iterated, sel, scores, first);
   if (i < n) mask[i] = ((act >> i) & 1ull) ? 0 : 1;
 }
 
@@ -1297,6 +1313,74 @@ int afl_krum_select(const double* D, int n, int f, int rounds, int iterated, int
   if (n < 1 || n > GMM_MAXN || f < 0 || f > n || rounds < 1 || rounds > n || (iterated != 0 && iterated != 1))
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_krum_select, dim3(1), dim3(64), 0, s, D, n, f, rounds, iterated, sel, mask, scores);
+  return (int)hipGetLastError();
+}
+
+// ============================================================================ agr_bisect
+// The AGR-tailored attacks on Krum / Multi-Krum / Bulyan (Shejwalkar & Houmansadr, NDSS 2021; docs/PARITY.md): the
+// whole bisection on gamma in ONE launch of one wave.  The modelled system has n' = K + m rows: the K genuine rows
+// (indices 0 .. K - 1, squared distances Dg [K][K] fp64, read as symmetric from the upper triangle) and m identical
+// copies of the candidate c(gamma) = mean - gamma dev (indices K .. n' - 1: last, so that every index tie goes against
+// the attacker), whose squared distance to genuine row j is d_j = max(A_j - 2 gamma B_j + gamma^2 C, 0) and to each
+// other 0.  Per gamma the wave rebuilds that n' x n' matrix in LDS and runs krum_select_wave on it:
+//   target 0 (Krum):       1 pick,            accepted when the pick is a copy;
+//   target 1 (Multi-Krum): n' - f picks,      scored once,            accepted when all m copies are picked;
+//   target 2 (Bulyan):     n' - 2 f picks,    re-scored every pick,   accepted when all m copies are picked.
+// A NaN in A, B or C rejects.  An accept moves gamma up by step / 2, a reject down; the state is bisect_decide's
+// (linalg.hip): st[0] the next gamma, st[1] the last accepted, st[2] the last tried, st[4 + i] the gamma tried at
+// iteration i, st[20 + i] 1.0 if it was accepted.  d_j is formed with individually rounded products and sums (no
+// contraction), the operation order of the composite, so that both sides see the same bits.
+// Every trip count is fixed by (n', f, target, n_iter); lane 0 writes the state with ordinary stores.
+__global__ void __launch_bounds__(64) k_agr_bisect(const double* __restrict__ Dg, const double* __restrict__ A,
+                                                   const double* __restrict__ B, const double* __restrict__ C, int K,
+                                                   int m, int f, int target, int n_iter, double step0,
+                                                   double* __restrict__ st) {
+  __shared__ double V[GMM_MAXN * KS_LD];
+  __shared__ unsigned char J[GMM_MAXN * KS_LD];
+  __shared__ double dj[GMM_MAXN];
+  const int i = threadIdx.x;
+  const int n = K + m;
+  const int rounds = target == 0 ? 1 : (target == 1 ? n - f : n - 2 * f);
+  const int iterated = target == 2 ? 1 : 0;
+  const unsigned long long copies = (n >= 64 ? ~0ull : ((1ull << n) - 1ull)) & ~((1ull << K) - 1ull);  // (K < 64)
+  const double a = i < K ? A[i] : 0.0, b = i < K ? B[i] : 0.0, c = C[0];
+  const bool bad = __any((a != a) || (b != b) || (c != c));
+  double g = st[0], step = step0;
+  for (int it = 0; it < n_iter; ++it) {
+    if (i < K) {
+      const double q = __dadd_rn(__dsub_rn(a, __dmul_rn(__dmul_rn(2.0, g), b)), __dmul_rn(__dmul_rn(g, g), c));
+      dj[i] = q > 0.0 ? q : 0.0;
+    }
+    __syncthreads();
+    for (int e = i; e < n * n; e += 64) {
+      const int r = e / n, cc = e - r * n;
+      const int lo = min(r, cc), hi = max(r, cc);
+      V[r * KS_LD + cc] = hi < K ? Dg[lo * K + hi] : (lo < K ? dj[lo] : 0.0);
+      J[r * KS_LD + cc] = (unsigned char)cc;
+    }
+    __syncthreads();
+    int first;
+    const unsigned long long act = krum_select_wave(V, J, n, f, rounds, iterated, nullptr, nullptr, first);
+    const bool acc = !bad && (target == 0 ? first >= K : (act & copies) == 0ull);
+    if (i == 0) {
+      st[BSA_TRIED + it] = g;
+      st[BSA_ACC + it] = acc ? 1.0 : 0.0;
+      st[2] = g;
+      if (acc) st[1] = g;
+      st[0] = acc ? g + step / 2.0 : g - step / 2.0;
+    }
+    g = acc ? g + step / 2.0 : g - step / 2.0;
+    step *= 0.5;
+    __syncthreads();  // (the next iteration overwrites the rows this one's lanes still walked)
+  }
+}
+
+int afl_agr_bisect(const double* Dg, const double* A, const double* B, const double* C, int K, int m, int f, int target,
+                   int n_iter, double gamma0, double* st, hipStream_t s) {
+  const long n = (long)K + m;
+  if (K < 1 || m < 1 || n > GMM_MAXN || n_iter < 1 || n_iter > 16 || !afl_agr_admissible(n, f, target))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_agr_bisect, dim3(1), dim3(64), 0, s, Dg, A, B, C, K, m, f, target, n_iter, gamma0, st);
   return (int)hipGetLastError();
 }
 

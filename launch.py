@@ -32,7 +32,9 @@ def parse_attackers(spec: str):
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description="attackfl_amd packed launcher")
     ap.add_argument("--config", default="config.yaml")
-    ap.add_argument("--attackers", default="", help="idx:mode:round[:arg...] comma-separated")
+    ap.add_argument("--attackers", default="",
+                    help="idx:mode:round[:arg...] comma-separated; mode: Random | LIE | Min-Max | Min-Sum | Opt-Fang | "
+                         "AGR-Krum | AGR-MKrum | AGR-Bulyan (AGR-tailored, args m:f:dev, e.g. 7:AGR-MKrum:2:2:2)")
     ap.add_argument("--device", default=None)
     ap.add_argument("--rounds", type=int, default=None, help="override server.num-round")
     args = ap.parse_args(argv)

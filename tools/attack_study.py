@@ -25,9 +25,20 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-MODES = ["fedavg", "median", "trimmed_mean", "krum", "hyper"]
-ATTACKS = {"none": None, "LIE": [0.74], "Min-Max": [], "Min-Sum": [], "Opt-Fang": [], "Random": [0.5]}
+MODES = ["fedavg", "median", "trimmed_mean", "krum", "hyper", "multi_krum", "bulyan"]
+# the AGR-tailored attacks (docs/PARITY.md) take [m, f]: [3, 3] for the 3-of-8 setting, f lowered by ``agr_args`` to
+# what the attacker's sample admits
+ATTACKS = {"none": None, "LIE": [0.74], "Min-Max": [], "Min-Sum": [], "Opt-Fang": [], "Random": [0.5],
+           "AGR-Krum": [3, 3], "AGR-MKrum": [3, 3], "AGR-Bulyan": [3, 3]}
 
+
+def agr_args(attack: str, K: int, m: int, f: int):
+    """[m, f] with f the largest value <= the wanted one that the modelled system of K genuine rows + m copies admits
+    (K + m >= 2 f + 3, AGR-Bulyan 4 f + 3; at least 1).  5 genuine clients and 3 attackers: f = 2 (Krum, Multi-Krum)
+    and f = 1 (Bulyan, also the server's f = auto at 8 clients) when every genuine model is sampled.  Where not even
+    f = 1 fits, the attack itself submits the attacker's own model (gamma 0)."""
+    per = 4 if attack == "AGR-Bulyan" else 2
+    return [m, max(1, min(f, (K + m - 3) // per))]
 
 def cells(spec: str):
     if spec:
@@ -36,7 +47,7 @@ def cells(spec: str):
 
 
 def run_cell(mode: str, attack: str, device: str, rounds: int, threads: int = 0, genuine_rate: float = 0.5,
-             distance: str = "spectral", seed: int = 7, tau: float = 1.0, attackers: int = 3) -> dict:
+             distance: str = "spectral", seed: int = 7, tau: float = None, attackers: int = 3) -> dict:
     import torch
 
     if threads:
@@ -58,7 +69,10 @@ def run_cell(mode: str, attack: str, device: str, rounds: int, threads: int = 0,
     }
     cfg = from_dict(d)
     who = range(8 - attackers, 8)
-    atk = {} if ATTACKS[attack] is None else {c: AttackSpec(attack, 2, ATTACKS[attack], tau=tau) for c in who}
+    args = ATTACKS[attack]
+    if attack.startswith("AGR-"):  # (K: the attacker's sample of the 8 - attackers genuine models, engine rule)
+        args = agr_args(attack, max(int(genuine_rate * (8 - attackers)), 1), attackers, int(args[1]))
+    atk = {} if args is None else {c: AttackSpec(attack, 2, args, tau=tau) for c in who}
     eng = FLEngine(cfg, device=device, table=build_client_table(cfg, 1, atk), verbose=False)
     t0 = time.time()
     stalled = False
@@ -70,8 +84,10 @@ def run_cell(mode: str, attack: str, device: str, rounds: int, threads: int = 0,
     eng.close()
     ok = [r for r in hist if r["ok"]]
     return {"device": "gpu" if device.startswith("cuda") else "cpu", "mode": mode, "attack": attack,
-            "genuine_rate": genuine_rate, "distance": distance, "seed": seed, "tau": tau,
-            "attackers": len(atk), "rounds": len(ok), "failed_rounds": len(hist) - len(ok), "stalled": stalled,
+            "genuine_rate": genuine_rate, "distance": distance, "seed": seed,
+            "tau": next((a.tau for a in atk.values()), 1.0 if tau is None else tau),
+            "attackers": len(atk), "attack_args": args, "rounds": len(ok), "failed_rounds": len(hist) - len(ok),
+            "stalled": stalled,
             "auc": [round(r["metric"], 5) for r in ok], "final_auc": round(ok[-1]["metric"], 5) if ok else None,
             "attack_gamma": [round(r["attack"]["gamma"], 4) for r in ok if "attack" in r and "gamma" in r["attack"]],
             # last ACCEPTED γ per attacking round (0: every tried γ was rejected)
@@ -95,7 +111,8 @@ def main() -> int:
     ap.add_argument("--jobs", type=int, default=1, help="parallel CPU processes")
     ap.add_argument("--genuine-rate", type=float, default=0.5, help="server.genuine-rate (reference default 0.5)")
     ap.add_argument("--distance", default="spectral", choices=["spectral", "flat"])
-    ap.add_argument("--tau", type=float, default=1.0, help="bisection stop gap (reference: 1.0)")
+    ap.add_argument("--tau", type=float, default=None,
+                    help="bisection stop gap (default: the attack's own, 1.0 as the reference, 0.02 for the AGR modes)")
     ap.add_argument("--attackers", type=int, default=3, help="attacking clients (the last N of 8)")
     ap.add_argument("--seeds", default="7", help="comma-separated run seeds (engine seed; server random-seed = seed - 6)")
     args = ap.parse_args()
