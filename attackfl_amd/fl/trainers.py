@@ -317,8 +317,8 @@ class _ResultRing:
 
 class FusedTrainer:
     """All local clients' local rounds in one persistent HIP launch: TransformerModel/ICU
-    (``ops/transformer.py``) and RNNModel/ICU (``ops/rnn.py``, falls back to the graph trainer when
-    its 3 workgroups per client do not all fit on the device)."""
+    (``ops/transformer.py``, 4 workgroups per client) and RNNModel/ICU (``ops/rnn.py``, falls back to the graph
+    trainer when its 3 workgroups per client do not all fit on the device)."""
 
     kind = "fused"
     MODELS = ("TransformerModel", "RNNModel")
@@ -389,7 +389,8 @@ class FusedTrainer:
         dev = self.device
         main = torch.cuda.current_stream(dev)
         cus = torch.cuda.get_device_properties(dev).multi_processor_count
-        side = 3 * ok.shape[0] * 2 <= cus
+        wgs = 3 if self.model_name == "RNNModel" else self.T.tf2_wgs()  # workgroups per client of the launch
+        side = wgs * ok.shape[0] * 2 <= cus
         if side:
             # ONE read-back stream per device for every trainer (FLTrust's server-model trainer too): a stream
             # waiting for a training blocks the hardware queue it is mapped to (GPU_MAX_HW_QUEUES = 4), and one

@@ -2,7 +2,8 @@
 trainer, and ``csrc/kernels/transformer.hip``, the global-workspace fallback and the eval kernels).
 
 ``train_clients`` runs ONE persistent kernel launch that trains every row of ``params [C, P]`` for all
-local epochs: by default the on-chip trainer (split 4: head | vitals | labs workgroups, 3 per client), in
+local epochs: by default the on-chip trainer (split 4: head half H0 | head half H1 | vitals | labs workgroups, 4 per
+client, ``tf2_wgs``), in
 back-to-back launches of the clients that fit when C exceeds one launch's co-residency budget
 (``auto_split``, ``chunked``); splits 1 / 2 / 3 are the global-workspace kernels (``transformer.hip``).  ``reference_train`` is the
 plain PyTorch fp32 oracle of exactly the same computation — same batches, same hash-generated dropout masks,
@@ -25,11 +26,19 @@ M32 = 0xFFFFFFFF
 
 
 # ------------------------------------------------------------------------------- device entry points
+def tf2_wgs() -> int:
+    """Workgroups per client of the on-chip trainer (``tf2.hip``), as the loaded native library reports them: 4 (two
+    head halves, two branches); a library from before the head was split has no such binding and runs 3."""
+    f = getattr(native(), "tf2_wgs_per_client", None)
+    return int(f()) if f is not None else 3
+
+
 def auto_split(C: int, dev) -> int:
     """Trainer variant for C clients, the first whose workgroups all fit on the device at once (one per CU):
-    4 = the on-chip trainer (``tf2.hip``: head | vitals | labs workgroups), in chunks of clients that fit when
-    C is larger (``onchip_capacity``).  The global-workspace kernels of ``transformer.hip`` (split 3 / 2 / 1) are
-    explicit choices (the tests' cross-checks) or the fallback below 3 CUs per process.  (A row-split variant —
+    4 = the on-chip trainer (``tf2.hip``: head half H0 | head half H1 | vitals | labs workgroups), in chunks of
+    clients that fit when C is larger (``onchip_capacity``).  The global-workspace kernels of ``transformer.hip``
+    (split 3 / 2 / 1) are explicit choices (the tests' cross-checks) or the fallback below ``tf2_wgs()`` CUs per
+    process.  (A row-split variant —
     each branch over two 4-wave workgroups, 5 per client — was built and measured slower in round 5, 91.5 vs
     103.6 rounds/s, ``profiles/ab_tf2_r5_row_split.log``, and removed.)"""
     from ..parallel.launcher import gpu_sharers
@@ -37,7 +46,7 @@ def auto_split(C: int, dev) -> int:
     # (processes sharing the GPU run their own persistent launches on the same CUs: count only this one's share)
     cus = torch.cuda.get_device_properties(dev).multi_processor_count // gpu_sharers()
     # more clients than fit run split 4 in back-to-back launches (train_clients_async), not the slower kernels
-    return 4 if cus >= 3 else 1
+    return 4 if cus >= tf2_wgs() else 1
 
 
 def client_chunks(C: int, cap: int) -> List[Tuple[int, int]]:
@@ -50,8 +59,9 @@ def client_chunks(C: int, cap: int) -> List[Tuple[int, int]]:
 
 
 def onchip_capacity(dev, wgs_per_client: int = 3) -> int:
-    """Clients per on-chip launch (tf2 / rnn2: 3 co-resident workgroups each) on this process's share of the
-    CUs; ``AFL_MAX_CLIENTS_PER_LAUNCH`` caps it (tests).  More clients run in back-to-back launches."""
+    """Clients per on-chip launch (``wgs_per_client`` co-resident workgroups each: rnn2 3, tf2 ``tf2_wgs()``) on this
+    process's share of the CUs; ``AFL_MAX_CLIENTS_PER_LAUNCH`` caps it (tests).  More clients run in back-to-back
+    launches."""
     from ..parallel.launcher import gpu_sharers
 
     cus = torch.cuda.get_device_properties(dev).multi_processor_count // gpu_sharers()
@@ -101,7 +111,7 @@ def train_clients_async(params: torch.Tensor, rows: torch.Tensor, order: torch.T
         return native().tf_train(p, rows_c, o, n, s, int(epochs), int(batch), float(lr), int(opt_mode),
                                  stamps if first else None, int(split), kt)
     if split == 4:  # (a stamped run stamps its first chunk only)
-        return chunked(launch, C, onchip_capacity(dev, 3), params, order_c, nd_t, seeds_t)
+        return chunked(launch, C, onchip_capacity(dev, tf2_wgs()), params, order_c, nd_t, seeds_t)
     return launch(params, order_c, nd_t, seeds_t)
 
 
@@ -138,7 +148,7 @@ def train_clients(params: torch.Tensor, rows: torch.Tensor, order: torch.Tensor,
 
     ``split``: workgroups per client — 1 (whole model in one workgroup), 2 (vitals branch + head |
     labs branch) or 3 (head | vitals | labs); the workgroups of a client hand activations and
-    gradients to each other every step.  4 = the on-chip trainer (``tf2.hip``, 3 workgroups per client,
+    gradients to each other every step.  4 = the on-chip trainer (``tf2.hip``, 4 workgroups per client,
     nothing of the model in global memory during the round).  Default: ``auto_split``.
     ``stamps``: optional device int64 [>=64] buffer receiving per-phase wall time (10 ns ticks) of
     workgroup ``stamps[63]`` of the first launch, summed over all steps (diagnostics)."""

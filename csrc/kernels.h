@@ -121,9 +121,14 @@ constexpr int AFL_TF_SYNC_WORDS = 4 * 8 * 32 + 32;  // per-wave flags (128-B lin
 // 2 directions x 2 branches x 8 waves x 4 KB of {value, tag} granules, zeroed with the flags every call
 constexpr int AFL_GR_WORDS = 2 * 2 * 8 * 1024;
 constexpr int AFL_TF2_SYNC_WORDS = AFL_TF_SYNC_WORDS + AFL_GR_WORDS;
+// tf2 only: then the export slots of the two head halves (tf2.hip head_main): 2 step parities x 8 row tiles x
+// 5 slots x 4 KB of granules, zeroed with the rest
+constexpr int AFL_EX_WORDS = 2 * 8 * 5 * 1024;
+constexpr int AFL_TF2H_SYNC_WORDS = AFL_TF2_SYNC_WORDS + AFL_EX_WORDS;
 // tf2.hip (TransformerModel / ICU fused training, on-chip edition: weights, Adam state and activations
-// in registers / LDS; 3 workgroups per client, sync words required)
+// in registers / LDS; 4 workgroups per client (afl_tf2_wgs_per_client), sync words [C][AFL_TF2H_SYNC_WORDS] required)
 int afl_tf2_train(const AflTfTrainArgs* a, hipStream_t s);
+int afl_tf2_wgs_per_client();
 int afl_tf2_train_stamped(const AflTfTrainArgs* a, hipStream_t s);  // tf2_stamps.hip: per-phase timers
 long afl_tf2_ws_floats();
 // determinism check of the on-chip trainers' cross-wave column sums (tf2.hip k_fxsum_test; tests only)

@@ -1,7 +1,8 @@
 // Fused TransformerModel/ICU local training, on-chip edition (reference training loop client.py:75-111,
 // model src/Model.py:166-246).  ONE persistent launch trains every client of a rank for all its local
-// epochs; each client runs on three co-resident 512-thread workgroups (head | vitals branch | labs
-// branch) that hand activations and gradients to each other once per direction per step.
+// epochs; each client runs on four co-resident 512-thread workgroups (head half H0 | head half H1 | vitals branch |
+// labs branch): the branches and the head hand activations and gradients to each other once per direction per step,
+// and the head halves exchange their rows once per step off the critical path (head_main).
 //
 // What differs from transformer.hip: after the prologue NOTHING of a client's model lives in global
 // memory.  Per workgroup:
@@ -106,7 +107,8 @@ constexpr int H_NVEC = 132;                        // fc1.b 64 | fc2.b 32 | outp
 constexpr int H_VEC = H_DZ2 + 8192;
 constexpr int H_PART = H_VEC + H_NVEC * 4;         // fp32 [8 waves][132] per-wave column sums (their gradients)
 constexpr int H_LOSS = H_PART + 8 * H_NVEC * 4;    // fp32 [8] per-wave loss partials, then u32 [8] their abort flags
-constexpr int H_TOTAL = H_LOSS + 64;
+constexpr int H_CNT = H_LOSS + 64;                 // u32: critical waves past their d(cat) hand-off (4 per step)
+constexpr int H_TOTAL = H_CNT + 16;
 enum { HV_B1 = 0, HV_B2 = 64, HV_WO = 96, HV_BO = 128 };
 
 constexpr int SMEM_CORE = B_TOTAL > H_TOTAL ? B_TOTAL : H_TOTAL;
@@ -136,7 +138,8 @@ constexpr long BR_UNITS = (long)CMP_SLOTS * NTH * 16;
 // [lane] float4 = m of the three tiles, v, then p
 constexpr long BR_SMALL = BR_UNITS + 8L * 12 * 64 * 16;
 constexpr long BR_WG_BYTES = BR_SMALL + 4L * 9 * 64 * 16;
-constexpr long WS_BYTES = WS_MOM + MOM_WG_BYTES + 2 * BR_WG_BYTES;  // head, vitals branch, labs branch
+constexpr long WS_MOM2 = WS_MOM + MOM_WG_BYTES + 2 * BR_WG_BYTES;   // head half H1's copy of the head's moments
+constexpr long WS_BYTES = WS_MOM2 + MOM_WG_BYTES;  // head half H0, vitals branch, labs branch, head half H1
 
 // branch LayerNorm column sums -> fp64 accumulator k of DBL (order G1 B1 G2 B2 G3 B3)
 __device__ __forceinline__ void ln_colsum(uchar* smem, int k, const float (&x)[16], int lane) {
@@ -1079,7 +1082,7 @@ __device__ __forceinline__ void branch_main(const AflTfTrainArgs& a, int cid, uc
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4;
   float* P = a.params + (long)cid * NPARAM;
   uchar* ws = (uchar*)(a.ws + (long)cid * a.ws_stride);
-  gu32* sync = (gu32*)(a.sync + (long)cid * AFL_TF2_SYNC_WORDS);
+  gu32* sync = (gu32*)(a.sync + (long)cid * AFL_TF2H_SYNC_WORDS);
   const __amdgpu_buffer_rsrc_t rg = gr_rsrc(sync);  // granule hand-off slots
   for (int i = tid; i < SMEM / 4; i += NTH) ldsf(smem, 0)[i] = 0.f;
   __syncthreads();
@@ -1194,18 +1197,53 @@ struct HdState {
   VS vec;
 };
 
-__device__ __forceinline__ void head_main(const AflTfTrainArgs& a, int cid, uchar* smem) {
+// The head runs as TWO workgroups, halves H0 (batch rows 0-63) and H1 (rows 64-127), so that every wave of the
+// step's critical section (hand-off in, forward, loss flags, backward, hand-off out) has a SIMD to itself: in one
+// workgroup the head waves w and w + 4 shared a SIMD, and the branch laggards (waves 4-7, the step's critical path)
+// were served by the younger head wave of each pair (profiles/ab_tf2_twin_head.log).
+//   * Hardware waves 0-3 of a half are its CRITICAL waves: wave c serves row tile 4 half + c — the 16 rows of branch
+//     wave 4 half + c — exactly as a head wave of the single workgroup did.
+//   * After its d(cat) hand-off a critical wave EXPORTS what the other half needs to hold the full 128-row state:
+//     the bf16 cat / a1 / dz1 / dz2 rows (the words it stores into its own LDS tiles), its fp32 column-sum partials
+//     and its loss partial, the NaN flag on the tag — EX_SLOTS granule slots (gr_put) per tile and step parity.
+//   * Hardware waves 4-7 are the IMPORTERS: wave 4 + c fetches row tile 4 (1 - half) + c of the partner and writes
+//     it into this half's LDS tiles, H_PART and H_LOSS at the partner's row / wave positions.  They wait on an LDS
+//     counter that their own half's critical waves signal after the d(cat) hand-off, so they issue nothing beside
+//     the critical section.
+//   * From the loss barrier on both halves run the single workgroup's code on all 8 waves — same tile ownership, same
+//     K order, same fixed-order partial sums, same Adam — on bit-identical inputs, so both hold bit-identical weights
+//     and nothing is sent back.  H1 has its own moment slab; only H0 writes losses, ok and the parameters.
+// Export slots are double-buffered by step parity.  Why export n + 2 cannot overwrite a slot before the partner's
+// import n has read it: export n + 2 follows this half's gr_get of the branches' step n + 2 outputs; those follow the
+// branches' update n + 1, whose counters need every branch wave's d(out) n + 1, i.e. the d(cat) hand-off of BOTH
+// halves' critical waves of step n + 1; the partner's critical waves start step n + 1 after the partner's
+// end-of-step-n barrier, which its importers reach only after import n.  (Single slots would race: export n + 1
+// needs only the partner's d(cat) n, which precedes its import n.)  Nothing rests on timing or placement; every wait
+// is bounded and raises XF_TMO.  A NaN flag reaches both halves (own rows: lossw, partner rows: the export tag) and
+// both branches (the d(cat) tag), so all four workgroups leave at the same step.
+constexpr int NWG = 4;       // workgroups per client: head halves H0, H1, vitals branch, labs branch
+constexpr int EX_SLOTS = 5;  // cat 2, a1 + dz1 2, {dz2, partials, loss} 1
+constexpr int EX_BASE = 2 * GR_DIR_BYTES;
+static_assert(EX_BASE == AFL_GR_WORDS * 4 && 2 * 8 * EX_SLOTS * 1024 == AFL_EX_WORDS, "export slots follow the hand-off slots");
+__device__ __forceinline__ int ex_off(int parity, int tile, int k, int lane) {
+  return EX_BASE + ((parity * 8 + tile) * EX_SLOTS + k) * 4096 + lane * 16;
+}
+
+__device__ __forceinline__ void head_main(const AflTfTrainArgs& a, int cid, uchar* smem, int half) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4;
-  const int r = 16 * wave + (lane & 15);
+  const bool crit = wave < 4;
+  // the row tile this wave serves (critical) or imports (importer), and this lane's batch row
+  const int tile = crit ? 4 * half + wave : 4 * (1 - half) + (wave - 4);
+  const int r = 16 * tile + (lane & 15);
   float* P = a.params + (long)cid * NPARAM;
   uchar* ws = (uchar*)(a.ws + (long)cid * a.ws_stride);
-  gu32* sync = (gu32*)(a.sync + (long)cid * AFL_TF2_SYNC_WORDS);
+  gu32* sync = (gu32*)(a.sync + (long)cid * AFL_TF2H_SYNC_WORDS);
   const __amdgpu_buffer_rsrc_t rg = gr_rsrc(sync);  // granule hand-off slots
   for (int i = tid; i < SMEM / 4; i += NTH) ldsf(smem, 0)[i] = 0.f;
   __syncthreads();
   HdState st;
   Stamp stp;
-  const __amdgpu_buffer_rsrc_t rm = rsrc(ws + WS_MOM);  // this workgroup's Adam moments
+  const __amdgpu_buffer_rsrc_t rm = rsrc(ws + (half == 0 ? WS_MOM : WS_MOM2));  // this workgroup's Adam moments
   mom_zero(rm, tid);
   {
     const int Ta = 2 * (wave & 3), Tb = 2 * (wave >> 2);
@@ -1229,7 +1267,6 @@ __device__ __forceinline__ void head_main(const AflTfTrainArgs& a, int cid, ucha
   const int nb_total = (nd + BS - 1) / BS;
   const uint32_t seed = a.seeds[cid];
   const uchar* vec = smem + H_VEC;
-  LDS_AS float* part = ldsf(smem, H_PART) + wave * H_NVEC;  // this wave's column sums
   LDS_AS float* lossw = ldsf(smem, H_LOSS);
   int step = 0;
   bool failed = false, timed_out = false;
@@ -1247,155 +1284,245 @@ __device__ __forceinline__ void head_main(const AflTfTrainArgs& a, int cid, ucha
   while (more) {
     // epoch boundaries crossed since the previous step (skipped batches included) close epoch losses
     while (cur_e < w.e) {
-      if (tid == 0) a.losses[(long)cid * E + cur_e] = epoch_loss / (float)max(nb_total, 1);
+      if (tid == 0 && half == 0) a.losses[(long)cid * E + cur_e] = epoch_loss / (float)max(nb_total, 1);
       epoch_loss = 0.f;
       ++cur_e;
     }
     ++step;
     const AdamK K = adam_k(a, step);
-    const uint32_t key = afl_hash32(seed, (uint32_t)step);
     const int Bn = min(BS, nd - w.b0);
-    const bool valid = r < Bn;
-    const float inv_bn = 1.f / (float)Bn;  // (before the wait: the division is off the critical path)
-    // fc1 dropout mask before the wait (the wave would only spin there)
-    const uint32_t mh = mask16(key, L_HEAD, r, g, THR_P03);
-    sb();
-    // ---- branch outputs of this wave's rows
+    // the tile's rows as the words its LDS tiles take (bf16 pairs), its loss partial and NaN flag: computed by the
+    // tile's critical wave, fetched from the partner's export by its importer
     u32x4 cv[4];  // vitals rows (cv[0..1]) | labs rows (cv[2..3])
-    const int go[2] = {gr_off(0, 0, wave, lane), gr_off(0, 1, wave, lane)};
-    const uint32_t fv = gr_get<2>(rg, go, cv, (uint32_t)step, 0, sync + XF_TMO, lane);
-    if (fv == 0xFFFFFFFFu) {
-      timed_out = failed = true;
-      break;
-    }
-    prio_hi();  // (head waves 0-3 below 4-7 measured -7 %: profiles/ab_tf2_r6_update.log)
-    stp(10, tid);
-    // (the dW operands of this step — cat, a1, dz1, dz2 tiles — and the head's column sums are written
-    // only AFTER the d(cat) hand-off below: they are off the branches' critical path)
-    // ---- fc1 + GELU + dropout(0.3)
-    float a1[16], gk1[16];
-    {
-      f4v acc[4];
-#pragma unroll
-      for (int T = 0; T < 4; ++T) {
-        acc[T] = Z4;
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-          acc[T] = mma(wfrag(smem + H_IMG_W1, HLD1, T, s, lane), __builtin_bit_cast(s8v, cv[s]), acc[T]);
+    u32x4 a1w[2], dz1w[2], dz2w;
+    float lsum = 0.f;
+    uint32_t wave_nan = 0u;
+    const int par = step & 1;
+    if (crit) {
+      const uint32_t key = afl_hash32(seed, (uint32_t)step);
+      const bool valid = r < Bn;
+      const float inv_bn = 1.f / (float)Bn;  // (before the wait: the division is off the critical path)
+      // fc1 dropout mask before the wait (the wave would only spin there)
+      const uint32_t mh = mask16(key, L_HEAD, r, g, THR_P03);
+      sb();
+      // ---- branch outputs of this wave's rows
+      const int go[2] = {gr_off(0, 0, tile, lane), gr_off(0, 1, tile, lane)};
+      const uint32_t fv = gr_get<2>(rg, go, cv, (uint32_t)step, 0, sync + XF_TMO, lane);
+      if (fv == 0xFFFFFFFFu) {
+        lds_signal(smem, H_CNT, lane);  // (the importers leave through their own bounded waits)
+        timed_out = failed = true;
+        break;
       }
-      float b1[16];
-      vec16(b1, vec + HV_B1 * 4, g);
+      prio_hi();  // (one critical wave per SIMD: the importers beside them sleep on H_CNT)
+      stp(10, tid);
+      // (the dW operands of this step — cat, a1, dz1, dz2 tiles — and the head's column sums are written
+      // only AFTER the d(cat) hand-off below: they are off the branches' critical path)
+      // ---- fc1 + GELU + dropout(0.3)
+      float a1[16], gk1[16];
+      {
+        f4v acc[4];
 #pragma unroll
-      for (int t = 0; t < 4; ++t)
+        for (int T = 0; T < 4; ++T) {
+          acc[T] = Z4;
 #pragma unroll
-        for (int i = 0; i < 4; i += 2) {
-          const int j = 4 * t + i;
-          gf2v gp;
-          const gf2v gl = gelu2(gf2v{acc[t][i] + b1[j], acc[t][i + 1] + b1[j + 1]}, gp);
+          for (int s = 0; s < 4; ++s)
+            acc[T] = mma(wfrag(smem + H_IMG_W1, HLD1, T, s, lane), __builtin_bit_cast(s8v, cv[s]), acc[T]);
+        }
+        float b1[16];
+        vec16(b1, vec + HV_B1 * 4, g);
 #pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            a1[j + h] = keepf(gl[h] * INV_K03, mh, j + h);
-            gk1[j + h] = keepf(gp[h] * INV_K03, mh, j + h);
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int i = 0; i < 4; i += 2) {
+            const int j = 4 * t + i;
+            gf2v gp;
+            const gf2v gl = gelu2(gf2v{acc[t][i] + b1[j], acc[t][i + 1] + b1[j + 1]}, gp);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              a1[j + h] = keepf(gl[h] * INV_K03, mh, j + h);
+              gk1[j + h] = keepf(gp[h] * INV_K03, mh, j + h);
+            }
           }
+      }
+      // ---- fc2 + GELU, output layer, sigmoid, BCE (log clamped at -100)
+      float dz2[8], gw[8];
+      float dy3 = 0.f, pl = 0.f;
+      {
+        const s8v b0 = bfrag(a1, 0), b1 = bfrag(a1, 1);
+        f4v acc[2];
+#pragma unroll
+        for (int T = 0; T < 2; ++T) {
+          acc[T] = mma(wfrag(smem + H_IMG_W2, HLD2, T, 0, lane), b0, Z4);
+          acc[T] = mma(wfrag(smem + H_IMG_W2, HLD2, T, 1, lane), b1, acc[T]);
         }
-    }
-    // ---- fc2 + GELU, output layer, sigmoid, BCE (log clamped at -100)
-    float dz2[8], gw[8];
-    float dy3 = 0.f, pl = 0.f;
-    {
-      const s8v b0 = bfrag(a1, 0), b1 = bfrag(a1, 1);
-      f4v acc[2];
+        float b2[8], wo[8], g2[8], gp2[8];
+        vec8(b2, vec + HV_B2 * 4, g);
+        vec8(wo, vec + HV_WO * 4, g);
+        float dot = 0.f;
 #pragma unroll
-      for (int T = 0; T < 2; ++T) {
-        acc[T] = mma(wfrag(smem + H_IMG_W2, HLD2, T, 0, lane), b0, Z4);
-        acc[T] = mma(wfrag(smem + H_IMG_W2, HLD2, T, 1, lane), b1, acc[T]);
-      }
-      float b2[8], wo[8], g2[8], gp2[8];
-      vec8(b2, vec + HV_B2 * 4, g);
-      vec8(wo, vec + HV_WO * 4, g);
-      float dot = 0.f;
+        for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; i += 2) {
-          const int j = 4 * t + i;
-          gf2v gp;
-          const gf2v gl = gelu2(gf2v{acc[t][i] + b2[j], acc[t][i + 1] + b2[j + 1]}, gp);
-          g2[j] = gl[0];
-          g2[j + 1] = gl[1];
-          gp2[j] = gp[0];
-          gp2[j + 1] = gp[1];
-          dot += g2[j] * wo[j];
-          dot += g2[j + 1] * wo[j + 1];
+          for (int i = 0; i < 4; i += 2) {
+            const int j = 4 * t + i;
+            gf2v gp;
+            const gf2v gl = gelu2(gf2v{acc[t][i] + b2[j], acc[t][i + 1] + b2[j + 1]}, gp);
+            g2[j] = gl[0];
+            g2[j + 1] = gl[1];
+            gp2[j] = gp[0];
+            gp2[j + 1] = gp[1];
+            dot += g2[j] * wo[j];
+            dot += g2[j + 1] * wo[j + 1];
+          }
+        const float y3 = fk::rsum4(dot) + *(const LDS_AS float*)(vec + HV_BO * 4);
+        const float p = sigmoidf_(y3);
+        if (valid) {
+          // torch's BCELoss gradient (p - y) / max(p (1 - p), 1e-12) times the sigmoid's p (1 - p), as one factor
+          // without a division (1 unless the sigmoid saturates; NaN propagates through the compare's false branch)
+          const float pq = p * (1.f - p);
+          dy3 = (p - lab) * (pq >= 1e-12f ? 1.f : pq * 1e12f) * inv_bn;
         }
-      const float y3 = fk::rsum4(dot) + *(const LDS_AS float*)(vec + HV_BO * 4);
-      const float p = sigmoidf_(y3);
-      if (valid) {
-        // torch's BCELoss gradient (p - y) / max(p (1 - p), 1e-12) times the sigmoid's p (1 - p), as one factor
-        // without a division (1 unless the sigmoid saturates; NaN propagates through the compare's false branch)
-        const float pq = p * (1.f - p);
-        dy3 = (p - lab) * (pq >= 1e-12f ? 1.f : pq * 1e12f) * inv_bn;
-      }
-      pl = p;
+        pl = p;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        dz2[j] = dy3 * wo[j] * gp2[j];
-        gw[j] = dy3 * g2[j];
-      }
-    }
-    // the NaN-loss abort rides on the hand-off tag: a row's loss is NaN exactly where its gradient factor dy3 is
-    // not finite (p or the label NaN; labels are 0 / 1), so the flag needs no loss on the critical path — the loss
-    // VALUE (logs, wave sum) is computed after the hand-off, and the head aborts on the same flags
-    const uint32_t wave_nan = __builtin_amdgcn_ballot_w64(!(fabsf(dy3) <= 3.402823466e38f)) != 0 ? 1u : 0u;
-    // ---- d a1 = dz2 . W2 -> d z1 = d a1 * drop'(.) * gelu'(z1)
-    float dz1[16];
-    {
-      const s8v bz = bfrag(dz2, 0);
-#pragma unroll
-      for (int T = 0; T < 4; ++T) {
-        const f4v acc = mma(wtfrag<true>(smem + H_IMG_W2, HLD2, T, 0, lane), bz, Z4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dz1[4 * T + i] = acc[i] * gk1[4 * T + i];
-      }
-    }
-    // ---- d cat = dz1 . W1, each half straight to its branch
-    {
-      const s8v b0 = bfrag(dz1, 0), b1 = bfrag(dz1, 1);
-#pragma unroll
-      for (int hb = 0; hb < 2; ++hb) {
-        float d[16];
-#pragma unroll
-        for (int Tl = 0; Tl < 4; ++Tl) {
-          const int T = 4 * hb + Tl;
-          f4v acc = mma(wtfrag<true>(smem + H_IMG_W1, HLD1, T, 0, lane), b0, Z4);
-          acc = mma(wtfrag<true>(smem + H_IMG_W1, HLD1, T, 1, lane), b1, acc);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) d[4 * Tl + i] = acc[i];
+        for (int j = 0; j < 8; ++j) {
+          dz2[j] = dy3 * wo[j] * gp2[j];
+          gw[j] = dy3 * g2[j];
         }
-        u32x4 u[2];
-        pack16(d, u);
-        gr_put(rg, gr_off(1, hb, wave, lane), u, ((uint32_t)step << 1) | wave_nan);  // NaN abort rides on the tag
       }
+      // the NaN-loss abort rides on the hand-off tag: a row's loss is NaN exactly where its gradient factor dy3 is
+      // not finite (p or the label NaN; labels are 0 / 1), so the flag needs no loss on the critical path — the loss
+      // VALUE (logs, wave sum) is computed after the hand-off, and the head aborts on the same flags
+      wave_nan = __builtin_amdgcn_ballot_w64(!(fabsf(dy3) <= 3.402823466e38f)) != 0 ? 1u : 0u;
+      // ---- d a1 = dz2 . W2 -> d z1 = d a1 * drop'(.) * gelu'(z1)
+      float dz1[16];
+      {
+        const s8v bz = bfrag(dz2, 0);
+#pragma unroll
+        for (int T = 0; T < 4; ++T) {
+          const f4v acc = mma(wtfrag<true>(smem + H_IMG_W2, HLD2, T, 0, lane), bz, Z4);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) dz1[4 * T + i] = acc[i] * gk1[4 * T + i];
+        }
+      }
+      // ---- d cat = dz1 . W1, each half straight to its branch
+      {
+        const s8v b0 = bfrag(dz1, 0), b1 = bfrag(dz1, 1);
+#pragma unroll
+        for (int hb = 0; hb < 2; ++hb) {
+          float d[16];
+#pragma unroll
+          for (int Tl = 0; Tl < 4; ++Tl) {
+            const int T = 4 * hb + Tl;
+            f4v acc = mma(wtfrag<true>(smem + H_IMG_W1, HLD1, T, 0, lane), b0, Z4);
+            acc = mma(wtfrag<true>(smem + H_IMG_W1, HLD1, T, 1, lane), b1, acc);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) d[4 * Tl + i] = acc[i];
+          }
+          u32x4 u[2];
+          pack16(d, u);
+          gr_put(rg, gr_off(1, hb, tile, lane), u, ((uint32_t)step << 1) | wave_nan);  // NaN abort rides on the tag
+        }
+      }
+      prio_lo();
+      lds_signal(smem, H_CNT, lane);  // this wave's hand-off is out: the importers may start polling
+      // ---- export this tile's rows to the partner half (bf16 pairs, the words the LDS tiles below take)
+      pack16(a1, a1w);
+      pack16(dz1, dz1w);
+      dz2w = u32x4{pk2(dz2[0], dz2[1]), pk2(dz2[2], dz2[3]), pk2(dz2[4], dz2[5]), pk2(dz2[6], dz2[7])};
+      const uint32_t xtag = ((uint32_t)step << 1) | wave_nan;
+      int xl = lane, xt = tile;  // (the export offsets rebuilt here from opaque indices, not held across the step)
+      asm volatile("" : "+v"(xl));
+      asm volatile("" : "+s"(xt));
+      const int xo = ex_off(par, xt, 0, xl);
+      {
+        const u32x4 c0[2] = {cv[0], cv[1]}, c1[2] = {cv[2], cv[3]};
+        gr_put(rg, xo, c0, xtag);
+        gr_put(rg, xo + 4096, c1, xtag);
+        gr_put(rg, xo + 2 * 4096, a1w, xtag);
+        gr_put(rg, xo + 3 * 4096, dz1w, xtag);
+      }
+      {  // the tile's loss partial (each row counted once: lane group 0), for the loss barrier
+        float lrow = 0.f;
+        if (valid) {
+          // clamp like torch.clamp: NaN must propagate (fmaxf would swallow it)
+          float lg, lg1;
+          bce_logs(pl, lg, lg1);
+          const float lp = lg < -100.f ? -100.f : lg, l1p = lg1 < -100.f ? -100.f : lg1;
+          lrow = -(lab * lp + (1.f - lab) * l1p);
+        }
+        lsum = wave_sum(xl < 16 ? lrow : 0.f);
+      }
+      {  // the tile's column sums (read after the loss barrier), then the last export slot
+        sb();
+        // (the partials' lane addresses from the opaque indices too: held across the step, one of them went to scratch)
+        LDS_AS float* pt = ldsf(smem, H_PART) + xt * H_NVEC;
+        float sb2, swo, sb1;
+        const int f2 = colsum32(dz2, xl, sb2), fo = colsum32(gw, xl, swo);
+        if (f2 >= 0) {
+          pt[HV_B2 + f2] = sb2;
+          pt[HV_WO + fo] = swo;
+        }
+        const int f1 = colsum64(dz1, xl, sb1);
+        pt[HV_B1 + f1] = sb1;
+        const float dbo = wave_sum(xl < 16 ? dy3 : 0.f);  // d output.bias
+        if (xl == 0) pt[HV_BO] = dbo;
+        // (the partials as stored, read back lane-major: entries 129..131 are never written and stay 0)
+        const LDS_AS float* pr = pt + xl;
+        const float p0 = pr[0], p1 = pr[64], p2 = xl < 4 ? pr[128] : 0.f;
+        const u32x4 c4[2] = {dz2w, u32x4{__float_as_uint(p0), __float_as_uint(p1), __float_as_uint(p2), __float_as_uint(lsum)}};
+        gr_put(rg, xo + 4 * 4096, c4, xtag);
+      }
+    } else {
+      // ---- importer: the partner half's export of row tile `tile`
+      prio_lo();
+      if (!lds_wait(smem, H_CNT, 4u * (uint32_t)step)) {
+        if (lane == 0) __hip_atomic_store(sync + XF_TMO, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        timed_out = failed = true;
+        break;
+      }
+      stp(10, tid);
+      int xl = lane, xt = tile;  // (offsets rebuilt here from opaque indices, not held across the step)
+      asm volatile("" : "+v"(xl));
+      asm volatile("" : "+s"(xt));
+      // (two sweeps, the slots written last first: one sweep of all five holds 120 registers)
+      const int xo = ex_off(par, xt, 0, xl);
+      const int eb[2] = {xo + 3 * 4096, xo + 4 * 4096};
+      u32x4 eu[4];
+      const uint32_t fv = gr_get<2>(rg, eb, eu, (uint32_t)step, 1, sync + XF_TMO, lane);
+      if (fv == 0xFFFFFFFFu) {
+        timed_out = failed = true;
+        break;
+      }
+      dz1w[0] = eu[0];
+      dz1w[1] = eu[1];
+      dz2w = eu[2];
+      LDS_AS float* pw = ldsf(smem, H_PART) + xt * H_NVEC + xl;
+      pw[0] = __uint_as_float(eu[3][0]);
+      pw[64] = __uint_as_float(eu[3][1]);
+      if (xl < 4) pw[128] = __uint_as_float(eu[3][2]);
+      lsum = __uint_as_float(eu[3][3]);
+      wave_nan = fv & 1u;
+      const int ea[3] = {xo, xo + 4096, xo + 2 * 4096};
+      u32x4 ev[6];
+      if (gr_get<3>(rg, ea, ev, (uint32_t)step, 1, sync + XF_TMO, lane) == 0xFFFFFFFFu) {
+        timed_out = failed = true;
+        break;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) cv[k] = ev[k];
+      a1w[0] = ev[4];
+      a1w[1] = ev[5];
     }
-    prio_lo();
-    {  // per-wave loss partial (each row counted once: lane group 0) and the abort flag, for the loss barrier
-      float lrow = 0.f;
-      if (valid) {
-        // clamp like torch.clamp: NaN must propagate (fmaxf would swallow it)
-        float lg, lg1;
-        bce_logs(pl, lg, lg1);
-        const float lp = lg < -100.f ? -100.f : lg, l1p = lg1 < -100.f ? -100.f : lg1;
-        lrow = -(lab * lp + (1.f - lab) * l1p);
-      }
-      const float lsum = wave_sum(g == 0 ? lrow : 0.f);
-      if (lane == 0) {
-        lossw[wave] = lsum;
-        lossw[8 + wave] = __uint_as_float(wave_nan);
-      }
-    }
-    // ---- deferred: dW operand tiles and column sums of this wave's rows (read after the loss barrier)
+    // ---- the tile's loss partial and abort flag, and its dW operand rows (read after the loss barrier)
     {
       sb();
+      int sl = lane, stl = tile;  // (the tile addresses rebuilt here from opaque indices, not held across the step)
+      asm volatile("" : "+v"(sl));
+      asm volatile("" : "+s"(stl));
+      const int r = 16 * stl + (sl & 15), g = sl >> 4;
+      if (sl == 0) {
+        lossw[stl] = lsum;
+        lossw[8 + stl] = __uint_as_float(wave_nan);
+      }
 #pragma unroll
       for (int t = 0; t < 8; ++t) {  // cat: tile t of the 8 = half (t & 1) of cv[t >> 1]
         const u32x4 u = cv[t >> 1];
@@ -1403,21 +1530,13 @@ __device__ __forceinline__ void head_main(const AflTfTrainArgs& a, int cid, ucha
         *(LDS_AS u32x2v*)(smem + H_CAT + t128(r, 4 * t + g)) = v;
       }
 #pragma unroll
-      for (int t = 0; t < 4; ++t) st4<TK64>(smem + H_A1, r, 4 * t + g, a1 + 4 * t);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) st4<TK32>(smem + H_DZ2, r, 4 * t + g, dz2 + 4 * t);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) st4<TK64>(smem + H_DZ1, r, 4 * t + g, dz1 + 4 * t);
-      float sb2, swo, sb1;
-      const int f2 = colsum32(dz2, lane, sb2), fo = colsum32(gw, lane, swo);
-      if (f2 >= 0) {
-        part[HV_B2 + f2] = sb2;
-        part[HV_WO + fo] = swo;
+      for (int t = 0; t < 4; ++t) {  // (words 2t, 2t + 1 of a row: what st4 packs from features 4t .. 4t + 3)
+        const int q = 2 * (t & 1);
+        *(LDS_AS u32x2v*)(smem + H_A1 + t64(r, 4 * t + g)) = u32x2v{a1w[t >> 1][q], a1w[t >> 1][q + 1]};
+        *(LDS_AS u32x2v*)(smem + H_DZ1 + t64(r, 4 * t + g)) = u32x2v{dz1w[t >> 1][q], dz1w[t >> 1][q + 1]};
       }
-      const int f1 = colsum64(dz1, lane, sb1);
-      part[HV_B1 + f1] = sb1;
-      const float dbo = wave_sum(g == 0 ? dy3 : 0.f);  // d output.bias
-      if (lane == 0) part[HV_BO] = dbo;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) *(LDS_AS u32x2v*)(smem + H_DZ2 + t32(r, 4 * t + g)) = u32x2v{dz2w[2 * t], dz2w[2 * t + 1]};
     }
     stp(11, tid);
     // Adam moments of this step's update (after the hand-off drain, before the loss barrier)
@@ -1511,12 +1630,14 @@ __device__ __forceinline__ void head_main(const AflTfTrainArgs& a, int cid, ucha
   stamp_fini(stp, a, smem, tid);
   if (!failed) {
     while (cur_e < E) {  // the last epoch (and trailing epochs that had no step)
-      if (tid == 0) a.losses[(long)cid * E + cur_e] = epoch_loss / (float)max(nb_total, 1);
+      if (tid == 0 && half == 0) a.losses[(long)cid * E + cur_e] = epoch_loss / (float)max(nb_total, 1);
       epoch_loss = 0.f;
       ++cur_e;
     }
   }
-  // parameters back (a failed client keeps its pre-step values: the failing step applied no update)
+  // parameters back, from H0 (H1 holds the same bits; a failed client keeps its pre-step values: the failing step
+  // applied no update)
+  if (half != 0) return;
   {
     int ln = lane, wv = wave;
     opq(ln, wv);  // (addresses recomputed here, not carried from the prologue's tile loads across the step loop)
@@ -1541,7 +1662,8 @@ __device__ __forceinline__ void head_main(const AflTfTrainArgs& a, int cid, ucha
 #else
 #define K_TF2 k_tf2_train
 #endif
-// 3 workgroups per client: blocks c (head), CP + c (vitals branch), 2 CP + c (labs branch).  Role-major block order
+// 4 workgroups per client: blocks c (head half H0), CP + c (head half H1), 2 CP + c (vitals branch), 3 CP + c (labs
+// branch).  Role-major block order
 // with a block stride CP padded to a multiple of 8 when the grid still fits: a client's workgroups are blocks
 // role * CP + cid, which the round-robin dispatch deals to ONE XCD (same-L2 hand-offs; speed only, never
 // correctness); padding blocks (cid >= C) exit at once.
@@ -1551,14 +1673,14 @@ __global__ void __launch_bounds__(t2::NTH) K_TF2(AflTfTrainArgs a) {
   const int role = blockIdx.x / cp, cid = blockIdx.x - role * cp;
   if (cid >= a.C) return;
 #if defined(TF2_ROLE)
-  if (TF2_ROLE == 0) t2::head_main(a, cid, smem);
-  else if (TF2_ROLE == 1) t2::branch_main<0>(a, cid, smem);
+  if (TF2_ROLE < 2) t2::head_main(a, cid, smem, TF2_ROLE);
+  else if (TF2_ROLE == 2) t2::branch_main<0>(a, cid, smem);
   else t2::branch_main<1>(a, cid, smem);
   (void)role;
 #else
-  if (role == 0)
-    t2::head_main(a, cid, smem);
-  else if (role == 1)
+  if (role < 2)
+    t2::head_main(a, cid, smem, role);
+  else if (role == 2)
     t2::branch_main<0>(a, cid, smem);
   else
     t2::branch_main<1>(a, cid, smem);
@@ -1599,6 +1721,7 @@ int afl_fxsum_test(const float* vals, int W, uint32_t seed, int mode, float* out
 int afl_tf2_train_stamped(const AflTfTrainArgs* a, hipStream_t s) {
 #else
 long afl_tf2_ws_floats() { return t2::WS_BYTES / 4; }
+int afl_tf2_wgs_per_client() { return t2::NWG; }
 
 int afl_tf2_train(const AflTfTrainArgs* a, hipStream_t s) {
   if (a->stamps) return afl_tf2_train_stamped(a, s);
@@ -1609,7 +1732,7 @@ int afl_tf2_train(const AflTfTrainArgs* a, hipStream_t s) {
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return -3;
-  const int wgs = 3;
+  const int wgs = t2::NWG;
   if (wgs * a->C > cus) return -4;  // the workgroups of a client spin on each other: all must be resident
   AflTfTrainArgs b = *a;
   b.cpad = (a->C + 7) / 8 * 8;

@@ -25,12 +25,14 @@ NAMES = {0: "F:G1 dense+E1", 1: "F:G2 vproj+E2", 2: "F:G3 oproj+E3 LN1", 3: "F:G
          10: "B:E10 LN bwd", 11: "B:A10+G11", 12: "B:E11", 13: "B:G12+dW2", 14: "B:E12 LN1 bwd", 15: "B:G13+dW1",
          16: "B:E13", 17: "B:(none)", 18: "B:G14+dWo", 19: "B:E14+dWv", 20: "B:E15+dWd",
          21: "X:publish+wait d(out)"}
-# on-chip trainer (split 4, tf2.hip): branch workgroups (blocks 3c+1, 3c+2) and the head (3c)
+# on-chip trainer (split 4, tf2.hip), role-major blocks: head halves H0, H1 (roles 0, 1), vitals and labs branches (2, 3).
+# Head stamps of a critical wave (0-3); an importer wave (4-7) stamps 10 = wait for its half's critical waves,
+# 11 = import of the partner's rows.
 NAMES4 = {0: "B:forward", 1: "B:publish+prefetch+masks+backward prologue", 2: "B:wait d(out)", 3: "B:backward",
           4: "B:leaders ffn tiles + wait counter A / laggards wait counter A, abort",
           5: "B:units (leaders out_proj + dense + small-unit Adam / laggards in_proj.v)",
           7: "B:vector Adam (owner-computed, no barrier)", 8: "B:end barrier", 10: "H:wait branches",
-          11: "H:fwd+loss+bwd+publish", 12: "H:bar+loss", 13: "H:dW+Adam", 14: "H:end barrier"}
+          11: "H:fwd+loss+bwd+publish+export", 12: "H:bar+loss", 13: "H:dW+Adam", 14: "H:end barrier"}
 
 def block_stride(clients: int, wgs: int, dev) -> int:
     """tf2.hip's role-major block stride: C padded to a multiple of 8 when the padded grid still fits."""
@@ -55,14 +57,14 @@ def main():
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--opt-mode", type=int, default=0, help="1 = SGD test mode (no Adam moments)")
     ap.add_argument("--split", type=int, default=0, help="workgroups per client (1, 2, 3); 0 = auto")
-    ap.add_argument("--block", type=int, default=0, help="workgroup whose phases are stamped (-1: 0, 1, 2 in turn)")
+    ap.add_argument("--block", type=int, default=0,
+                    help="workgroup (role) whose phases are stamped (-1: every role in turn; tf2 has 4, the others 3)")
     ap.add_argument("--model", default="TransformerModel")
     ap.add_argument("--wave", type=int, default=0, help="stamping wave of the workgroup (-1: 0..7 in turn; tf2 only)")
     args = ap.parse_args()
     if args.model == "RNNModel":
         return main_rnn(args)
     dev = torch.device("cuda", 0)
-    blocks = [0, 1, 2] if args.block < 0 else [args.block]
     ds = synthetic_icu(60000, seed=3)
     rows = torch.cat([ds.vitals, ds.labs, ds.labels[:, None]], 1).to(dev)
     lay = ParamLayout.for_model("TransformerModel")
@@ -75,6 +77,7 @@ def main():
                     split=split)
     torch.cuda.synchronize()
     used = split or T.auto_split(args.clients, dev)
+    blocks = list(range(T.tf2_wgs() if used == 4 else 3)) if args.block < 0 else [args.block]
     for b in blocks:
         for wv in (range(8) if args.wave < 0 else [args.wave]):
             run(args, dev, rows, order, plan, params, split, used, b, wv)
@@ -84,7 +87,7 @@ def run(args, dev, rows, order, plan, params, split, used, block, wave=0):
     names = NAMES4 if used == 4 else NAMES
     stamps = torch.zeros(64, dtype=torch.int64, device=dev)
     # role-major block order: role r of client 0 is block r * CP (the padded stride of the on-chip trainers)
-    stamps[63] = block * (block_stride(args.clients, 3, dev) if used == 4 else args.clients)
+    stamps[63] = block * (block_stride(args.clients, T.tf2_wgs(), dev) if used == 4 else args.clients)
     stamps[62] = wave
     t0 = time.perf_counter()
     T.train_clients(params.clone(), rows, order, plan.nd, args.epochs, 128, 0.004, list(range(args.clients)),
