@@ -43,6 +43,7 @@ from ..data import DeviceTable, resolve_dataset
 from ..detect import HyperDetector
 from ..eval import Validation
 from ..models import ParamLayout, build_model
+from ..ops import onchip
 from ..parallel.comm import Comm, LoopbackComm
 from ..utils import trace
 from ..utils.ckpt import CheckpointWriter
@@ -1096,10 +1097,7 @@ class FLEngine:
         queued beside it on another stream starts before it ends."""
         if self.device.type != "cuda" or getattr(self.trainer, "kind", "") != "graph" or self.model_name != "CNNModel":
             return False
-        from ..parallel.launcher import gpu_sharers
-
-        cus = torch.cuda.get_device_properties(self.device).multi_processor_count // gpu_sharers()
-        return len(self.local) * int(ops.native().cnn2_wgs_per_client()) >= cus
+        return len(self.local) * int(ops.native().cnn2_wgs_per_client()) >= onchip.cu_share(self.device)
 
     def _prefetch_validation(self, g: Optional[torch.Tensor]) -> None:
         """Ahead of a speculative launch that fills the GPU: this round's validation forward + AUC go in FIRST

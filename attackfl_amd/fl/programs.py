@@ -24,6 +24,7 @@ import torch
 
 from ..models import ParamLayout
 from ..ops import layers as Lx
+from ..ops import onchip
 from ..ops.layers import ACT_RELU, StepCtl
 
 VIT, LAB = 7, 16
@@ -653,25 +654,10 @@ class ProgramRunner:
         if os.environ.get("AFL_CNN2", "1") == "0" or pg.B > 128 or pg.B < 2 or params.dtype != torch.float32:
             return False  # (the kernel needs 2 <= B <= 128: hipErrorInvalidValue otherwise)
         from .. import ops
-        from ..parallel.launcher import gpu_sharers
 
-        nat = ops.native()
-        # every workgroup of a launch must be resident at once; processes sharing the GPU run their own persistent
-        # launches on the same CUs, so a launch may count on only its share of them.  More clients than that run
-        # in back-to-back launches of clients that fit (_train_cnn2), never on the layer program.
-        cus = torch.cuda.get_device_properties(params.device).multi_processor_count // gpu_sharers()
-        return int(nat.cnn2_wgs_per_client()) <= cus
-
-    def cnn2_capacity(self, device) -> int:
-        """Clients per cnn2 launch: every workgroup co-resident on this process's share of the CUs
-        (``AFL_MAX_CLIENTS_PER_LAUNCH`` caps it further: the chunking tests)."""
-        from .. import ops
-        from ..parallel.launcher import gpu_sharers
-
-        cus = torch.cuda.get_device_properties(device).multi_processor_count // gpu_sharers()
-        cap = max(1, cus // int(ops.native().cnn2_wgs_per_client()))
-        lim = int(os.environ.get("AFL_MAX_CLIENTS_PER_LAUNCH", "0") or 0)
-        return min(cap, lim) if lim > 0 else cap
+        # more clients than one launch holds run in back-to-back launches of clients that fit (_train_cnn2), never
+        # on the layer program
+        return int(ops.native().cnn2_wgs_per_client()) <= onchip.cu_share(params.device)
 
     def _train_cnn2(self, table, params, plan, lr, ctl, sync, opt_mode: int = 0):
         from .. import ops
@@ -700,9 +686,7 @@ class ProgramRunner:
             live = []
             # back-to-back launches of at most `cap` clients (balanced), each a full persistent round: a client's
             # result does not depend on which launch or how many clients train it (placement independence)
-            from ..ops.transformer import client_chunks
-
-            for a, b in client_chunks(C, self.cnn2_capacity(dev)):
+            for a, b in onchip.client_chunks(C, onchip.capacity(dev, int(nat.cnn2_wgs_per_client()))):
                 cc = zi[C:C + (b - a) * int(nat.cnn2_ctr_words())]  # (zeroed by the step-table launch)
                 if a > 0:  # (later chunks: counters left by the previous chunk's launch)
                     cc.zero_()

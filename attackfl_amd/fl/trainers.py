@@ -12,8 +12,8 @@ Semantics follow the reference trainers (``client.py:66-131``):
 Two implementations share one sampling plan (``make_plan``), so they see identical batches:
 * ``EagerTrainer``  — PyTorch modules + ``torch.optim.Adam`` (the CPU path and the oracle);
 * ``FusedTrainer``  — ONE persistent HIP kernel launch trains all of a rank's clients for all
-  their local epochs (one workgroup per client, weights/activations in LDS, Adam state in
-  registers) — ``ops/transformer.py``.  TransformerModel/ICU on gfx950.
+  their local epochs (co-resident workgroups per client, model and Adam state on chip) — ``ops/transformer.py``,
+  ``ops/rnn.py``; launch policy in ``ops/onchip.py``.  TransformerModel/ICU and RNNModel/ICU on gfx950.
 * ``GraphTrainer``  — client-batched layer programs (``fl/programs.py``: CNNModel, RNNModel,
   TransformerClassifier/HAR) whose optimizer step is captured once into a HIP graph and replayed.
 """
@@ -316,9 +316,8 @@ class _ResultRing:
 
 
 class FusedTrainer:
-    """All local clients' local rounds in one persistent HIP launch: TransformerModel/ICU
-    (``ops/transformer.py``, 4 workgroups per client) and RNNModel/ICU (``ops/rnn.py``, falls back to the graph
-    trainer when its 3 workgroups per client do not all fit on the device)."""
+    """All local clients' local rounds in one persistent HIP launch: TransformerModel/ICU (``ops/transformer.py``)
+    and RNNModel/ICU (``ops/rnn.py``), each described by its ``ops.onchip.Trainer``."""
 
     kind = "fused"
     MODELS = ("TransformerModel", "RNNModel")
@@ -328,11 +327,11 @@ class FusedTrainer:
             raise ValueError("fused trainer supports TransformerModel/ICU and RNNModel/ICU")
         if torch.device(device).type != "cuda":
             raise ValueError("fused trainer needs a GPU")
-        from ..ops import rnn as R
-        from ..ops import transformer as T
+        from ..ops import onchip, rnn, transformer
 
         self.model_name = model_name
-        self.T, self.R = T, R
+        self.onchip = onchip
+        self.desc = {t.model: t for t in (transformer.TRAINER, rnn.TRAINER)}[model_name]
         self.table = table
         self.device = torch.device(device)
         self.layout = ParamLayout.for_model(model_name)
@@ -346,23 +345,17 @@ class FusedTrainer:
 
     def device_seed(self, s: int) -> int:
         """The kernel's int32 form of client seed ``s`` (the engine stages these on the device)."""
-        return (self.R if self.model_name == "RNNModel" else self.T).device_seed(s)
+        return self.desc.device_seed(s)
 
     def launch(self, params: torch.Tensor, plan: Plan, lr: float, batch: int, seeds: Sequence[int],
                seeds_dev: Optional[torch.Tensor] = None) -> Pending:
         """``seeds_dev``: the same seeds already on the device in ``device_seed`` form (optional)."""
-        if self.model_name == "RNNModel":
-            if not self.R.fits(params.shape[0], self.device):
-                if self._fallback is None:
-                    self._fallback = GraphTrainer(self.model_name, "ICU", self.table, self.device, self.verbose)
-                return self._fallback.launch(params, plan, lr, batch, seeds)
-            ok, losses = self.R.train_clients_async(params, self.table.rows, plan.order, _nd(plan), plan.epochs, batch,
-                                                    lr, seeds if seeds_dev is None else seeds_dev)
-            what = "fused RNN trainer"
-        else:
-            ok, losses = self.T.train_clients_async(params, self.table.rows, plan.order, _nd(plan), plan.epochs, batch,
-                                                    lr, seeds if seeds_dev is None else seeds_dev)
-            what = "fused trainer"
+        if self.desc.capacity(self.device) < 1:  # not even one client's workgroups fit: the layer program
+            if self._fallback is None:
+                self._fallback = GraphTrainer(self.model_name, "ICU", self.table, self.device, self.verbose)
+            return self._fallback.launch(params, plan, lr, batch, seeds)
+        ok, losses = self.desc.launch(params, self.table.rows, plan.order, _nd(plan), plan.epochs, batch, lr,
+                                      seeds if seeds_dev is None else seeds_dev)
 
         # ok + losses come back in ONE asynchronous copy into a pinned buffer, and result() waits on an event
         # (two blocking .cpu() reads cost two host round trips between the round's training and its aggregate)
@@ -375,7 +368,7 @@ class FusedTrainer:
                 time.sleep(0)
             okh = buf[:, 0].to(torch.int32)
             if bool((okh < 0).any()):
-                raise RuntimeError(f"{what}: a cross-workgroup hand-off timed out (workgroups not co-resident?)")
+                raise RuntimeError(f"{self.desc.what}: a cross-workgroup hand-off timed out (workgroups not co-resident?)")
             return [bool(x) for x in okh.tolist()], buf[:, 1:].clone()
 
         return Pending(fin, ok, losses)
@@ -388,9 +381,8 @@ class FusedTrainer:
         stream the copy could wait behind the NEXT launch's persistent workgroups)."""
         dev = self.device
         main = torch.cuda.current_stream(dev)
-        cus = torch.cuda.get_device_properties(dev).multi_processor_count
-        wgs = 3 if self.model_name == "RNNModel" else self.T.tf2_wgs()  # workgroups per client of the launch
-        side = wgs * ok.shape[0] * 2 <= cus
+        cus = self.onchip.device_cus(dev)  # (deliberately the whole device, not cu_share: what the copy competes with)
+        side = self.desc.wgs() * ok.shape[0] * 2 <= cus
         if side:
             # ONE read-back stream per device for every trainer (FLTrust's server-model trainer too): a stream
             # waiting for a training blocks the hardware queue it is mapped to (GPU_MAX_HW_QUEUES = 4), and one

@@ -1,88 +1,35 @@
-"""Fused TransformerModel/ICU training and evaluation (HIP kernels in ``csrc/kernels/tf2.hip``, the on-chip
-trainer, and ``csrc/kernels/transformer.hip``, the global-workspace fallback and the eval kernels).
+"""Fused TransformerModel/ICU local training and evaluation (``csrc/kernels/tf2.hip``, on-chip, split 4;
+``transformer.hip``, the global-workspace kernels as splits 1 / 2 / 3 and the eval kernels): one launch trains all
+of a rank's clients for all their local epochs, four co-resident workgroups per client (head half H0 | head half
+H1 | vitals | labs).  The launch policy (co-residency, chunking) is ``ops/onchip.py``.
 
-``train_clients`` runs ONE persistent kernel launch that trains every row of ``params [C, P]`` for all
-local epochs: by default the on-chip trainer (split 4: head half H0 | head half H1 | vitals | labs workgroups, 4 per
-client, ``tf2_wgs``), in
-back-to-back launches of the clients that fit when C exceeds one launch's co-residency budget
-(``auto_split``, ``chunked``); splits 1 / 2 / 3 are the global-workspace kernels (``transformer.hip``).  ``reference_train`` is the
-plain PyTorch fp32 oracle of exactly the same computation — same batches, same hash-generated dropout masks,
-Adam (or the SGD test mode) — used by the numerics tests to check the kernels.
+``reference_train`` is the plain PyTorch fp32 oracle of exactly the same computation (same batches, same
+hash-generated dropout masks, Adam or the SGD test mode), used by the numerics tests to check the kernels.
 """
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, Sequence, Tuple
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import native
-from .rnn import _dev_i32, _on
+from . import native, onchip
 
 NPARAM = 47693
 M32 = 0xFFFFFFFF
 
 
 # ------------------------------------------------------------------------------- device entry points
-def tf2_wgs() -> int:
-    """Workgroups per client of the on-chip trainer (``tf2.hip``), as the loaded native library reports them: 4 (two
-    head halves, two branches); a library from before the head was split has no such binding and runs 3."""
-    f = getattr(native(), "tf2_wgs_per_client", None)
-    return int(f()) if f is not None else 3
-
-
 def auto_split(C: int, dev) -> int:
-    """Trainer variant for C clients, the first whose workgroups all fit on the device at once (one per CU):
-    4 = the on-chip trainer (``tf2.hip``: head half H0 | head half H1 | vitals | labs workgroups), in chunks of
-    clients that fit when C is larger (``onchip_capacity``).  The global-workspace kernels of ``transformer.hip``
-    (split 3 / 2 / 1) are explicit choices (the tests' cross-checks) or the fallback below ``tf2_wgs()`` CUs per
-    process.  (A row-split variant —
-    each branch over two 4-wave workgroups, 5 per client — was built and measured slower in round 5, 91.5 vs
-    103.6 rounds/s, ``profiles/ab_tf2_r5_row_split.log``, and removed.)"""
-    from ..parallel.launcher import gpu_sharers
-
-    # (processes sharing the GPU run their own persistent launches on the same CUs: count only this one's share)
-    cus = torch.cuda.get_device_properties(dev).multi_processor_count // gpu_sharers()
-    # more clients than fit run split 4 in back-to-back launches (train_clients_async), not the slower kernels
-    return 4 if cus >= tf2_wgs() else 1
-
-
-def client_chunks(C: int, cap: int) -> List[Tuple[int, int]]:
-    """[a, b) client ranges of at most ``cap`` clients, as few launches as possible, balanced."""
-    if C <= 0:
-        return []
-    n = -(-C // max(1, cap))
-    size = -(-C // n)
-    return [(a, min(C, a + size)) for a in range(0, C, size)]
-
-
-def onchip_capacity(dev, wgs_per_client: int = 3) -> int:
-    """Clients per on-chip launch (``wgs_per_client`` co-resident workgroups each: rnn2 3, tf2 ``tf2_wgs()``) on this
-    process's share of the CUs; ``AFL_MAX_CLIENTS_PER_LAUNCH`` caps it (tests).  More clients run in back-to-back
-    launches."""
-    from ..parallel.launcher import gpu_sharers
-
-    cus = torch.cuda.get_device_properties(dev).multi_processor_count // gpu_sharers()
-    cap = max(1, cus // wgs_per_client)
-    lim = int(os.environ.get("AFL_MAX_CLIENTS_PER_LAUNCH", "0") or 0)
-    return min(cap, lim) if lim > 0 else cap
-
-
-def chunked(launch, C: int, cap: int, params, order, nd_t, seeds_t):
-    """Run ``launch(params, order, nd, seeds, first) -> (ok, losses)`` over client chunks of at most ``cap``
-    clients, back to back on the current stream (``first``: the chunk that takes the diagnostic stamps, if any);
-    the per-chunk device results are concatenated (no host sync)."""
-    parts = client_chunks(C, cap)
-    if len(parts) <= 1:
-        return launch(params, order, nd_t, seeds_t, True)
-    oks, losses = [], []
-    for i, (a, b) in enumerate(parts):
-        ok, ls = launch(params[a:b], order[a:b], nd_t[a:b], seeds_t[a:b], i == 0)
-        oks.append(ok)
-        losses.append(ls)
-    return torch.cat(oks), torch.cat(losses)
+    """Trainer variant for C clients: 4, the on-chip trainer (``tf2.hip``), whenever one client's workgroups fit
+    on this process's share of the CUs; more clients than one launch holds run split 4 in back-to-back launches
+    (``onchip.chunked``), never the slower kernels.  Below that share 1, the one-workgroup kernel of
+    ``transformer.hip``, which needs no co-residency; splits 2 and 3 are explicit choices (the tests' cross-checks).
+    (A row-split variant, each branch over two 4-wave workgroups, 5 per client, was built and measured slower in
+    round 5, 91.5 vs 103.6 rounds/s, ``profiles/ab_tf2_r5_row_split.log``, and removed.)"""
+    return 4 if onchip.cu_share(dev) >= TRAINER.wgs() else 1
 
 
 def device_seed(s: int) -> int:
@@ -95,64 +42,33 @@ def train_clients_async(params: torch.Tensor, rows: torch.Tensor, order: torch.T
                         lr: float, seeds: Sequence[int], opt_mode: int = 0, stamps: torch.Tensor = None,
                         split: int = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Enqueue the training launch on the current stream and return (ok [C] int32, losses [C, E]) as
-    DEVICE tensors without synchronising (see ``finish``); arguments as ``train_clients``."""
-    dev = params.device
+    DEVICE tensors without synchronising (see ``onchip.finish``); arguments as ``train_clients``."""
     C = params.shape[0]
     if split is None:  # (AFL_TF_SPLIT: A/B override of the automatic choice)
-        split = int(os.environ.get("AFL_TF_SPLIT", "0") or 0) or (auto_split(C, dev) if C > 0 else 1)
-    nd_t = _dev_i32(nd, dev)
-    seeds_t = seeds if _on(seeds, dev) else torch.tensor([device_seed(s) for s in seeds], dtype=torch.int32, device=dev)
-    kt = None
-    if split == 4:
-        kt = adam_step_table(float(lr), int(epochs) * -(-int(order.shape[2]) // int(batch)), dev)
-    rows_c, order_c = rows.contiguous(), order.contiguous()
+        split = int(os.environ.get("AFL_TF_SPLIT", "0") or 0) or (auto_split(C, params.device) if C > 0 else 1)
 
-    def launch(p, o, n, s, first=True):
-        return native().tf_train(p, rows_c, o, n, s, int(epochs), int(batch), float(lr), int(opt_mode),
-                                 stamps if first else None, int(split), kt)
-    if split == 4:  # (a stamped run stamps its first chunk only)
-        return chunked(launch, C, onchip_capacity(dev, tf2_wgs()), params, order_c, nd_t, seeds_t)
-    return launch(params, order_c, nd_t, seeds_t)
-
-
-_KT_CACHE: Dict[tuple, torch.Tensor] = {}
-
-
-def adam_step_table(lr: float, steps: int, dev) -> torch.Tensor:
-    """[n >= steps, 2] fp32 device table of torch.optim.Adam's per-step scalars, computed in double like
-    torch does on the host: (lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)) for t = 1..n.  Cached per (lr,
-    device) and grown in powers of two, so a round never uploads it again."""
-    key = (lr, str(dev))
-    t = _KT_CACHE.get(key)
-    if t is None or t.shape[0] < steps:
-        n = 1 << max(10, (max(steps, 1) - 1).bit_length())
-        tt = np.arange(1, n + 1, dtype=np.float64)
-        tab = np.stack([lr / (1.0 - 0.9 ** tt), 1.0 / np.sqrt(1.0 - 0.999 ** tt)], axis=1).astype(np.float32)
-        t = _KT_CACHE[key] = torch.from_numpy(tab).to(dev)
-    return t
-
-
-def finish(ok: torch.Tensor, losses: torch.Tensor, what: str = "fused trainer") -> Tuple[torch.Tensor, torch.Tensor]:
-    """Synchronise on a launch from ``train_clients_async`` -> host (ok, losses); a negative ok means a
-    cross-workgroup hand-off timed out."""
-    ok = ok.cpu()
-    if bool((ok < 0).any()):
-        raise RuntimeError(f"{what}: a cross-workgroup hand-off timed out (workgroups not co-resident?)")
-    return ok, losses.cpu()
+    def train(p, r, o, n, s, kt, st):
+        return native().tf_train(p, r, o, n, s, int(epochs), int(batch), float(lr), int(opt_mode), st, int(split), kt)
+    steps = int(epochs) * -(-int(order.shape[2]) // int(batch)) if split == 4 else None
+    return onchip.enqueue(TRAINER, train, params, rows, order, nd, seeds, stamps, lr, steps, chunk=split == 4)
 
 
 def train_clients(params: torch.Tensor, rows: torch.Tensor, order: torch.Tensor, nd, epochs: int, batch: int,
                   lr: float, seeds: Sequence[int], opt_mode: int = 0, stamps: torch.Tensor = None,
                   split: int = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Train all clients in place. Returns (ok [C] int32 on host, losses [C, E] fp32 on host).
+    """Train ``params [C, 47693]`` in place.  Returns (ok [C] int32, losses [C, E]) on the host.
 
-    ``split``: workgroups per client — 1 (whole model in one workgroup), 2 (vitals branch + head |
-    labs branch) or 3 (head | vitals | labs); the workgroups of a client hand activations and
-    gradients to each other every step.  4 = the on-chip trainer (``tf2.hip``, 4 workgroups per client,
-    nothing of the model in global memory during the round).  Default: ``auto_split``.
+    ``split``: 4 = the on-chip trainer (``tf2.hip``: weights, optimizer state and activations in registers / LDS
+    for the whole round); 1 / 2 / 3 = the global-workspace kernels of ``transformer.hip`` with that many
+    workgroups per client (whole model | vitals + head, labs | head, vitals, labs).  Default: ``auto_split``.
     ``stamps``: optional device int64 [>=64] buffer receiving per-phase wall time (10 ns ticks) of
-    workgroup ``stamps[63]`` of the first launch, summed over all steps (diagnostics)."""
-    return finish(*train_clients_async(params, rows, order, nd, epochs, batch, lr, seeds, opt_mode, stamps, split))
+    workgroup ``stamps[63]`` of the first launch, summed over all steps (tools/phase_profile.py)."""
+    return onchip.finish(*train_clients_async(params, rows, order, nd, epochs, batch, lr, seeds, opt_mode, stamps,
+                                              split), what=TRAINER.what)
+
+
+TRAINER = onchip.Trainer(model="TransformerModel", nparam=NPARAM, wgs=lambda: int(native().tf2_wgs_per_client()),
+                         device_seed=device_seed, launch=train_clients_async, what="fused trainer")
 
 
 def eval_forward(params: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:

@@ -738,9 +738,28 @@ torch::Tensor make_plan(torch::Tensor seeds, torch::Tensor nd, int64_t n_train, 
   return order;
 }
 
-// Fused whole-round trainers: kind 0 = TransformerModel (split 1 / 2 / 3 workgroups per client; split 4 = the on-chip
-// trainer, tf2_wgs_per_client() workgroups per client),
-// kind 1 = RNNModel (always 3 workgroups per client).
+// Fused whole-round trainers, one row each: the global-workspace kernels (transformer.hip with 1 / 2 / 3 workgroups per
+// client, rnn.hip) and the on-chip trainers (tf2.hip, rnn2.hip: state in registers / LDS, Adam step table kt).
+struct FusedTrainerRow {
+  int (*param_count)();
+  long (*ws_floats)();
+  long sync_words;  // zeroed hand-off words per client
+  int wgs;          // workgroups per client (AflTfTrainArgs::split)
+  int (*launch)(const AflTfTrainArgs*, hipStream_t);
+};
+const FusedTrainerRow* fused_trainer_row(int kind, int64_t split) {
+  static const FusedTrainerRow rows[] = {
+      {afl_tf_param_count, afl_tf_ws_floats, 0, 1, afl_tf_train},
+      {afl_tf_param_count, afl_tf_ws_floats, AFL_TF_SYNC_WORDS, 2, afl_tf_train},
+      {afl_tf_param_count, afl_tf_ws_floats, AFL_TF_SYNC_WORDS, 3, afl_tf_train},
+      {afl_tf_param_count, afl_tf2_ws_floats, AFL_TF2H_SYNC_WORDS, afl_tf2_wgs_per_client(), afl_tf2_train},
+      {afl_rnn_param_count, afl_rnn_ws_floats, AFL_TF_SYNC_WORDS, 3, afl_rnn_train},
+      {afl_rnn_param_count, afl_rnn2_ws_floats, AFL_TF2_SYNC_WORDS, 3, afl_rnn2_train},
+  };
+  if (kind == 0) return &rows[split - 1];  // TransformerModel: split 1..4, 4 = tf2
+  return &rows[split == 4 ? 5 : 4];        // RNNModel: split 4 = rnn2, anything else rnn
+}
+
 std::vector<torch::Tensor> fused_train(int kind, torch::Tensor params, torch::Tensor rows, torch::Tensor order,
                                        torch::Tensor nd, torch::Tensor seeds, int64_t epochs, int64_t batch, double lr,
                                        int64_t opt_mode, c10::optional<torch::Tensor> stamps, int64_t split,
@@ -750,21 +769,17 @@ std::vector<torch::Tensor> fused_train(int kind, torch::Tensor params, torch::Te
   check_dev(order, "order", torch::kInt32);
   check_dev(nd, "nd", torch::kInt32);
   check_dev(seeds, "seeds", torch::kInt32);
-  const long P = kind == 0 ? afl_tf_param_count() : afl_rnn_param_count();
+  TORCH_CHECK(kind == 1 || (split >= 1 && split <= 4), "TransformerModel trainer split must be 1..4, got ", split);
+  const FusedTrainerRow& t = *fused_trainer_row(kind, split);
+  const long P = t.param_count();
   TORCH_CHECK(params.dim() == 2 && params.size(1) == P, "params must be [C, ", P, "]");
   TORCH_CHECK(rows.dim() == 2 && rows.size(1) == 24, "rows must be [N, 24]");
   const int C = params.size(0);
   TORCH_CHECK(order.dim() == 3 && order.size(0) == C && order.size(1) == epochs, "order must be [C, E, maxnd]");
   TORCH_CHECK(batch >= 2 && batch <= 128, "fused trainer supports batch sizes 2..128");
-  TORCH_CHECK(kind == 1 || (split >= 1 && split <= 4), "TransformerModel trainer split must be 1..4, got ", split);
-  // split 4 = the on-chip trainers (tf2.hip: 4 workgroups per client, rnn2.hip: 3; state in registers / LDS)
-  const bool tf2 = kind == 0 && split == 4, rnn2 = kind == 1 && split == 4;
-  const long wsf = tf2 ? afl_tf2_ws_floats() : rnn2 ? afl_rnn2_ws_floats() : kind == 0 ? afl_tf_ws_floats() : afl_rnn_ws_floats();
-  const long stride = ((wsf + 63) / 64) * 64;
+  const long stride = ((t.ws_floats() + 63) / 64) * 64;
   auto ws = torch::empty({(long)C * stride}, params.options());
-  const int split_eff = kind == 1 ? 3 : (int)std::max<int64_t>(1, split);  // (rnn2: 3 workgroups per client, tf2: 4)
-  const long sync_words =
-      split_eff > 1 ? (long)C * (tf2 ? AFL_TF2H_SYNC_WORDS : rnn2 ? AFL_TF2_SYNC_WORDS : AFL_TF_SYNC_WORDS) : 0;
+  const long sync_words = (long)C * t.sync_words;
   // ok [C] | losses [C, E] | the hand-off words (16-byte aligned): ONE zero fill per launch
   const long head = ((long)C + (long)C * epochs + 3) / 4 * 4;
   auto zero = torch::zeros({head + sync_words}, order.options());
@@ -802,14 +817,13 @@ std::vector<torch::Tensor> fused_train(int kind, torch::Tensor params, torch::Te
     a.kt = kt->data_ptr<float>();
     a.kt_n = (int)kt->size(0);
   }
-  a.split = split_eff;
+  a.split = t.wgs;
   a.cpad = 0;  // (the on-chip launchers pad the role-major block stride themselves)
-  if (a.split > 1) a.sync = (uint32_t*)zero.data_ptr<int>() + head;  // branch-parallel: zeroed hand-off words
-  const int rc = tf2 ? afl_tf2_train(&a, cur()) : rnn2 ? afl_rnn2_train(&a, cur())
-                 : kind == 0 ? afl_tf_train(&a, cur()) : afl_rnn_train(&a, cur());
+  if (t.wgs > 1) a.sync = (uint32_t*)zero.data_ptr<int>() + head;  // branch-parallel: zeroed hand-off words
+  const int rc = t.launch(&a, cur());
   TORCH_CHECK(rc != -4, "branch-parallel fused trainer needs workgroups-per-client * C <= CUs (all workgroups resident at "
               "once; tf2: tf2_wgs_per_client() = ", afl_tf2_wgs_per_client(), ", otherwise the split): launch at most "
-              "onchip_capacity(dev, workgroups per client) clients at a time (ops/transformer.py chunked; "
+              "onchip.capacity(dev, workgroups per client) clients at a time (ops/onchip.py chunked; "
               "AFL_MAX_CLIENTS_PER_LAUNCH caps it)");
   TORCH_CHECK(rc != -5, "on-chip trainer: Adam step table (kt) missing or shorter than the round");
   TORCH_CHECK(rc == 0, "fused trainer launch failed (", rc, ")");

@@ -110,6 +110,23 @@ struct AflTfTrainArgs {
   // fits, so a client's workgroups land on one XCD whatever C is); blocks with client index >= C exit
   int cpad;
 };
+// What every fused-trainer launcher checks before it launches `kernel` with `wgs` workgroups per client, in this order:
+// -1 batch outside [bmin, bmax] or the hand-off words missing (need_sync), -5 the Adam step table missing or shorter
+// than the round (need_kt), -2 the dynamic-LDS attribute, -3 the CU query, -4 not all workgroups resident at once
+// (the workgroups of a client spin on each other; one workgroup per CU).  A one-workgroup launch needs no
+// co-residency and makes no query.  *cus (optional): the device's CU count.
+inline int afl_launch_preamble(const AflTfTrainArgs* a, int bmin, int bmax, bool need_sync, bool need_kt,
+                               const void* kernel, int smem, int wgs, int* cus = nullptr) {
+  if (a->batch > bmax || a->batch < bmin || (need_sync && !a->sync)) return -1;
+  if (need_kt && (!a->kt || a->kt_n < a->E * ((a->maxnd + a->batch - 1) / a->batch))) return -5;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) return -2;
+  if (wgs == 1) return 0;
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return -3;
+  if (cus) *cus = n;
+  return wgs * a->C > n ? -4 : 0;
+}
 int afl_tf_train(const AflTfTrainArgs* a, hipStream_t s);
 int afl_tf_eval_bf(const float* params, unsigned short* bf, const float* rows, int n, float* out, hipStream_t s);
 // C models (params + c * pstride) over the same rows in one launch pair; bf = C * bfstride ushorts of scratch

@@ -632,14 +632,7 @@ long afl_rnn_ws_floats() { return WS_FLOATS; }
 int afl_rnn_param_count() { return NPARAM; }
 
 int afl_rnn_train(const AflTfTrainArgs* a, hipStream_t s) {
-  if (a->batch > BM || a->batch < 1 || !a->sync) return -1;
-  if (hipFuncSetAttribute((const void*)k_rnn_train, hipFuncAttributeMaxDynamicSharedMemorySize, S_TOTAL) != hipSuccess)
-    return -2;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                              hipSuccess)
-    return -3;
-  if (3 * a->C > cus) return -4;  // the three workgroups of every client spin on each other: all resident
+  if (const int rc = afl_launch_preamble(a, 1, BM, true, false, (const void*)k_rnn_train, S_TOTAL, 3)) return rc;
   hipLaunchKernelGGL(k_rnn_train, dim3(3 * a->C), dim3(NT), S_TOTAL, s, *a);
   return 0;
 }

@@ -1346,14 +1346,7 @@ int afl_rnn2_train(const AflTfTrainArgs* a, hipStream_t s) {
   if (a->stamps) return afl_rnn2_train_stamped(a, s);
 #endif
 #endif
-  if (a->batch > 128 || a->batch < 2 || !a->sync) return -1;
-  if (!a->kt || a->kt_n < a->E * ((a->maxnd + a->batch - 1) / a->batch)) return -5;  // step table too short
-  if (hipFuncSetAttribute((const void*)K_RNN2, hipFuncAttributeMaxDynamicSharedMemorySize, r2::SMEM) != hipSuccess)
-    return -2;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return -3;
-  if (3 * a->C > cus) return -4;  // the workgroups of a client spin on each other: all must be resident
+  if (const int rc = afl_launch_preamble(a, 2, 128, true, true, (const void*)K_RNN2, r2::SMEM, 3)) return rc;
   hipLaunchKernelGGL(K_RNN2, dim3(3 * a->C), dim3(oc::NTH), r2::SMEM, s, *a);
   return 0;
 }

@@ -1726,14 +1726,9 @@ int afl_tf2_wgs_per_client() { return t2::NWG; }
 int afl_tf2_train(const AflTfTrainArgs* a, hipStream_t s) {
   if (a->stamps) return afl_tf2_train_stamped(a, s);
 #endif
-  if (a->batch > 128 || a->batch < 2 || !a->sync) return -1;
-  if (!a->kt || a->kt_n < a->E * ((a->maxnd + a->batch - 1) / a->batch)) return -5;  // step table too short
-  if (hipFuncSetAttribute((const void*)K_TF2, hipFuncAttributeMaxDynamicSharedMemorySize, t2::SMEM) != hipSuccess) return -2;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return -3;
   const int wgs = t2::NWG;
-  if (wgs * a->C > cus) return -4;  // the workgroups of a client spin on each other: all must be resident
+  int cus = 0;
+  if (const int rc = afl_launch_preamble(a, 2, 128, true, true, (const void*)K_TF2, t2::SMEM, wgs, &cus)) return rc;
   AflTfTrainArgs b = *a;
   b.cpad = (a->C + 7) / 8 * 8;
 #ifdef TF2_NO_PAD  // A/B variant: the unpadded role-major grid

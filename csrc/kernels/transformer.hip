@@ -1192,26 +1192,16 @@ int afl_tf_bf_ushorts() { return BF_TOTAL; }
 int afl_tf_param_count() { return NPARAM; }
 
 int afl_tf_train(const AflTfTrainArgs* a, hipStream_t s) {
-  if (a->batch > BM || a->batch < 1) return -1;
-  const int wgs = a->sync ? a->split : 1;  // workgroups per client
+  const int wgs = a->sync ? a->split : 1;  // workgroups per client; the caller zeroes the sync words before every launch
   if (wgs < 1 || wgs > 3) return -1;
   const void* fn = wgs == 3 ? (const void*)k_tf_train_bp3 : (wgs == 2 ? (const void*)k_tf_train_bp : (const void*)k_tf_train);
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, S_TOTAL) != hipSuccess) return -2;
-  if (wgs > 1) {
-    // the workgroups of a client spin on each other: every workgroup must be resident at once
-    // (one 158 KB-LDS workgroup per CU); the caller zeroes the sync words before every launch
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -3;
-    if (wgs * a->C > cus) return -4;
-    if (wgs == 3)
-      hipLaunchKernelGGL(k_tf_train_bp3, dim3(3 * a->C), dim3(NT), S_TOTAL, s, *a);
-    else
-      hipLaunchKernelGGL(k_tf_train_bp, dim3(2 * a->C), dim3(NT), S_TOTAL, s, *a);
-  } else {
+  if (const int rc = afl_launch_preamble(a, 1, BM, false, false, fn, S_TOTAL, wgs)) return rc;
+  if (wgs == 3)
+    hipLaunchKernelGGL(k_tf_train_bp3, dim3(3 * a->C), dim3(NT), S_TOTAL, s, *a);
+  else if (wgs == 2)
+    hipLaunchKernelGGL(k_tf_train_bp, dim3(2 * a->C), dim3(NT), S_TOTAL, s, *a);
+  else
     hipLaunchKernelGGL(k_tf_train, dim3(a->C), dim3(NT), S_TOTAL, s, *a);
-  }
   return 0;
 }
 

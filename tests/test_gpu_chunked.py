@@ -1,4 +1,4 @@
-"""More clients than one persistent launch holds (ops.transformer.chunked / ProgramRunner._train_cnn2): the
+"""More clients than one persistent launch holds (ops.onchip.chunked / ProgramRunner._train_cnn2): the
 on-chip trainers run back-to-back launches of clients that fit, and a client's result is bit-identical to
 the one-launch run (placement independence) — reference server.py:58 takes any client count."""
 import pytest

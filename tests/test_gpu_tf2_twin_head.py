@@ -15,6 +15,7 @@ import torch
 import test_gpu_transformer as G
 from attackfl_amd.fl.trainers import make_plan
 from attackfl_amd.models import ParamLayout
+from attackfl_amd.ops import onchip
 from attackfl_amd.ops import transformer as T
 
 pytestmark = pytest.mark.gpu
@@ -125,11 +126,11 @@ def test_nan_in_one_half(gpu, pos):
 
 
 def test_one_client_more_than_a_launch_holds(gpu):
-    """onchip_capacity(gpu, 4) + 1 clients of 4 rows, 1 epoch: two launches, every client trains, and the result is
+    """onchip.capacity(gpu, 4) + 1 clients of 4 rows, 1 epoch: two launches, every client trains, and the result is
     bit-equal to the same clients launched as the two chunks explicitly."""
-    cap = T.onchip_capacity(gpu, 4)
+    cap = onchip.capacity(gpu, 4)
     C = cap + 1
-    parts = T.client_chunks(C, cap)
+    parts = onchip.client_chunks(C, cap)
     assert len(parts) == 2
     rows, base, _ = G._setup(1, [4])
     params = base.repeat(C, 1) * (1.0 + 1e-3 * torch.arange(C, dtype=torch.float32)[:, None])

@@ -5,6 +5,7 @@ import torch
 from attackfl_amd.data import DeviceTable, synthetic_icu
 from attackfl_amd.fl.trainers import make_plan
 from attackfl_amd.models import ParamLayout, build_model
+from attackfl_amd.ops import onchip
 from attackfl_amd.ops import transformer as T
 
 pytestmark = pytest.mark.gpu
@@ -182,7 +183,7 @@ def test_auto_split_choice(gpu):
     assert T.auto_split(8, gpu) == 4
     assert T.auto_split(cus // 3, gpu) == 4
     assert T.auto_split(cus // 3 + 1, gpu) == 4  # more clients: back-to-back split-4 launches (chunked)
-    assert T.onchip_capacity(gpu) == cus // 3
+    assert onchip.capacity(gpu, 3) == cus // 3
 
 
 def test_cross_wave_column_sums_are_order_independent(gpu):

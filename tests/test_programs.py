@@ -204,7 +204,7 @@ def test_attention_rc_keep_rate_within_3_sigma():
 
 
 def test_client_chunks_balanced():
-    from attackfl_amd.ops.transformer import client_chunks
+    from attackfl_amd.ops.onchip import client_chunks
 
     assert client_chunks(8, 85) == [(0, 8)]
     assert client_chunks(128, 85) == [(0, 64), (64, 128)]

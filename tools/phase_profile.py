@@ -77,7 +77,7 @@ def main():
                     split=split)
     torch.cuda.synchronize()
     used = split or T.auto_split(args.clients, dev)
-    blocks = list(range(T.tf2_wgs() if used == 4 else 3)) if args.block < 0 else [args.block]
+    blocks = list(range(T.TRAINER.wgs() if used == 4 else 3)) if args.block < 0 else [args.block]
     for b in blocks:
         for wv in (range(8) if args.wave < 0 else [args.wave]):
             run(args, dev, rows, order, plan, params, split, used, b, wv)
@@ -87,7 +87,7 @@ def run(args, dev, rows, order, plan, params, split, used, block, wave=0):
     names = NAMES4 if used == 4 else NAMES
     stamps = torch.zeros(64, dtype=torch.int64, device=dev)
     # role-major block order: role r of client 0 is block r * CP (the padded stride of the on-chip trainers)
-    stamps[63] = block * (block_stride(args.clients, T.tf2_wgs(), dev) if used == 4 else args.clients)
+    stamps[63] = block * (block_stride(args.clients, T.TRAINER.wgs(), dev) if used == 4 else args.clients)
     stamps[62] = wave
     t0 = time.perf_counter()
     T.train_clients(params.clone(), rows, order, plan.nd, args.epochs, 128, 0.004, list(range(args.clients)),
