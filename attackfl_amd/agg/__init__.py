@@ -15,7 +15,8 @@ Each rule returns ``AggResult(params [P] | None, ok, info)``.  Rows are in clien
   norm clip + cosine filter + FedAvg of the kept originals
 * fltracer      ``src/Utils.py:359-369`` (dormant in the reference)  PCA(1) + MAD z-score
 * byzantine     ``src/Utils.py:218-248`` (dead code in the reference) cosine ≥ 0.9 to model 0
-Beyond the reference (docs/PARITY.md): multi_krum, bulyan, dnc (assumed Byzantine count ``byz-f``) and geomed (RFA).
+Beyond the reference (docs/PARITY.md): multi_krum, bulyan, dnc (assumed Byzantine count ``byz-f``), geomed (RFA) and
+cclip (centred clipping about the global model the round started from: the one rule that takes ``centre``).
 FLTrust and the hypernetwork live in the engine (``fl/engine.py`` ``_fltrust``, ``fl/hyper_server.py``): they train.
 """
 from __future__ import annotations
@@ -155,6 +156,36 @@ def geomed(U: torch.Tensor, sizes=None, geomed_iters: int = 100, geomed_nu: floa
     return AggResult(ops.weighted_rows(U, w), True, {"weights": w, "iters": iters, "objective": obj})
 
 
+def cclip(U: torch.Tensor, sizes=None, centre: Optional[torch.Tensor] = None, cclip_iters: int = 3, cclip_tau="auto",
+          **_) -> AggResult:
+    """Centred clipping (Karimireddy, He & Jaggi, ICML 2021; one iteration = norm bounding, Sun et al. 2019; beyond the
+    reference, rule text in docs/PARITY.md): from v = ``centre`` (the global model the round started from; the
+    alpha-weighted mean of the rows when None), ``cclip_iters`` times v <- v + sum_i alpha_i s_i (x_i - v) with
+    s_i = min(1, tau / ||x_i - v||), alpha = sizes / sum sizes.  ``cclip_tau``: a radius > 0 or ``"auto"``, the lower
+    median of the first iteration's distances.  Run in Gram space (``k_cclip_weights`` on the Gram about the centre,
+    ``afl_gram_anchored``): the rows are read by the Gram pass and by the final row pass only.  No host read.  With a
+    centre a non-finite row is left out (its alpha not redistributed) and the result is the centre when no row is
+    finite; without one it makes the result non-finite, as FedAvg's is.  Always a new tensor."""
+    n = U.shape[0]
+    iters = int(cclip_iters)
+    auto = cclip_tau is None or (isinstance(cclip_tau, str) and cclip_tau == "auto")
+    tau = 0.0 if auto else float(cclip_tau)
+    if iters < 1 or not (auto or tau > 0):
+        raise ValueError(f"cclip needs cclip-iters >= 1 and cclip-tau 'auto' or > 0 (got {cclip_iters}, {cclip_tau}).")
+    a = torch.ones(n, dtype=torch.float64) if sizes is None else sizes
+    a = _device_weights(a, U.device)
+    alpha = a / a.sum()
+    if centre is None:
+        c, t, clipped, _ = ops.cclip_weights(ops.centred_gram(U), alpha, alpha, iters, "auto" if auto else tau)
+        out = ops.weighted_rows(U, c)
+    else:
+        g = centre.to(device=U.device, dtype=torch.float32)
+        c, t, clipped, _ = ops.cclip_weights(ops.gram_anchored(U, g), alpha, torch.zeros_like(alpha), iters,
+                                             "auto" if auto else tau)
+        out = ops.anchored_rows(U, c, g)
+    return AggResult(out, True, {"weights": c, "tau": t, "clipped": clipped, "iters": iters})
+
+
 def dnc(U: torch.Tensor, sizes=None, byz_f="auto", dnc_iters: int = 1, dnc_sub_dim: int = 10000, dnc_c: float = 1.0,
         seed: int = 0, **_) -> AggResult:
     """Divide-and-Conquer (Shejwalkar & Houmansadr, NDSS 2021; beyond the reference, rule text in docs/PARITY.md):
@@ -282,6 +313,7 @@ AGGREGATORS = {
     "bulyan": bulyan,
     "geomed": geomed,
     "dnc": dnc,
+    "cclip": cclip,
     "shieldfl": shieldfl,
     "gmm": gmm,
     "scionfl": scionfl,

@@ -24,9 +24,9 @@ Extensions (all optional, defaults keep reference behaviour):
   synthetic: auto | true | false   (auto = use the reference pickles when present)
   train-size / test-size / seed / har-train-size / har-test-size
 ``server:``
-  mode: the reference's modes plus multi_krum | bulyan | geomed | dnc (Multi-Krum, Bulyan, the geometric median /
-        RFA and Divide-and-Conquer: defences that assume f >= 1 Byzantine clients; ``krum`` keeps the reference's
-        f = 0, A-11; definitions in docs/PARITY.md)
+  mode: the reference's modes plus multi_krum | bulyan | geomed | dnc | cclip (Multi-Krum, Bulyan, the geometric
+        median / RFA, Divide-and-Conquer and centred clipping: defences that assume f >= 1 Byzantine clients;
+        ``krum`` keeps the reference's f = 0, A-11; definitions in docs/PARITY.md)
 ``engine:``
   trainer: auto | fused | graph | eager | oracle  (fused = HIP persistent TransformerModel / RNNModel
                                     kernels; graph = HIP-graph-replayed layer programs for CNN/RNN/HAR models;
@@ -60,6 +60,9 @@ Extensions (all optional, defaults keep reference behaviour):
   dnc-iters: int >= 1               (dnc: independent column sub-samples whose keep masks are intersected, default 1)
   dnc-sub-dim: int >= 1             (dnc: columns per sub-sample, default 10000; >= P uses every column)
   dnc-c: float > 0                  (dnc: the filtering fraction, ceil(c f) rows dropped per iteration, default 1.0)
+  cclip-iters: int >= 1             (cclip: clipping iterations, all of them run, default 3; 1 = norm bounding)
+  cclip-tau: auto | float > 0       (cclip: the clipping radius; auto, the default = the lower median of the rows'
+                                    distances to the round's starting model, found on the device every round)
   save-state: bool                  (write {model}.state.pt + {model}.clients.r{rank}.pt every round)
   resume: bool                      (continue from those files: counters, RNGs, optimizer moments)
 """
@@ -73,7 +76,7 @@ from typing import Any, Dict, List, Optional
 import yaml
 
 SERVER_MODES = ("fedavg", "hyper", "FLTrust", "trimmed_mean", "shieldfl", "gmm", "krum", "median", "scionfl",
-                "fltracer", "byzantine", "multi_krum", "bulyan", "geomed", "dnc")
+                "fltracer", "byzantine", "multi_krum", "bulyan", "geomed", "dnc", "cclip")
 ATTACK_MODES = ("Random", "Min-Max", "Min-Sum", "Opt-Fang", "LIE", "AGR-Krum", "AGR-MKrum", "AGR-Bulyan")
 # the AGR-tailored attacks (beyond the reference; docs/PARITY.md) and the rule each one models
 AGR_ATTACK_TARGETS = {"AGR-Krum": "krum", "AGR-MKrum": "mkrum", "AGR-Bulyan": "bulyan"}
@@ -133,7 +136,7 @@ EXTENSION_DEFAULTS: Dict[str, Any] = {
                "phase-sync": False, "fault-inject": [], "save-state": False, "resume": False,
                "speculative": True, "compat-har-train": False, "compat-fedavg-alias": False, "gmm-rank": 1,
                "byz-f": "auto", "geomed-iters": 100, "geomed-nu": 1e-6, "dnc-iters": 1, "dnc-sub-dim": 10000,
-               "dnc-c": 1.0},
+               "dnc-c": 1.0, "cclip-iters": 3, "cclip-tau": "auto"},
 }
 
 
@@ -319,6 +322,15 @@ class Config:
             c_ok = False
         if not c_ok:
             raise ValueError(f"engine.dnc-c must be a number > 0 (got {c!r})")
+        it, tau = self.engine.get("cclip-iters", 3), self.engine.get("cclip-tau", "auto")
+        if isinstance(it, bool) or not isinstance(it, int) or it < 1:
+            raise ValueError(f"engine.cclip-iters must be an integer >= 1 (got {it!r})")
+        try:  # (a YAML string such as "1e-3" is a number here too)
+            tau_ok = tau == "auto" or (not isinstance(tau, bool) and float(tau) > 0)
+        except (TypeError, ValueError):
+            tau_ok = False
+        if not tau_ok:
+            raise ValueError(f"engine.cclip-tau must be 'auto' or a number > 0 (got {tau!r})")
         return self
 
     def to_dict(self) -> Dict[str, Any]:

@@ -360,6 +360,36 @@ def geomed_weights(G: torch.Tensor, alpha: torch.Tensor, iters: int = 100, nu: f
     return composite.geomed_weights(G, alpha.to(G.device), int(iters), float(nu))
 
 
+def gram_anchored(U: torch.Tensor, anchor: torch.Tensor) -> torch.Tensor:
+    """n x n Gram of the rows about an external centre, <U_i - anchor, U_j - anchor> (fp64).  Device, n <= 64: one
+    pass of the fp64-MFMA Gram kernel centred on ``anchor`` (``afl_gram_anchored``)."""
+    if _dev(U) and 1 <= U.shape[0] <= 64:
+        return native().gram_anchored(U.to(torch.float32).contiguous(),
+                                      anchor.to(device=U.device, dtype=torch.float32).contiguous())
+    return composite.gram_anchored(U, anchor.to(U.device))
+
+
+def cclip_weights(G: torch.Tensor, alpha: torch.Tensor, c0: torch.Tensor, iters: int = 3, tau="auto"):
+    """Centred-clipping coefficients from a Gram matrix -> (c [n] fp64, tau, rows clipped in the last iteration, finite
+    rows), the last three 0-d tensors on G's device.  ``tau``: ``"auto"`` (the lower median of the first iteration's
+    finite distances, found on the device) or a number > 0.  Device, n <= 64: ``k_cclip_weights``."""
+    t = 0.0 if tau is None or (isinstance(tau, str) and tau == "auto") else float(tau)
+    if _dev(G) and G.shape[0] <= 64:
+        f64 = lambda x: x.to(device=G.device, dtype=torch.float64).contiguous()
+        c, info = native().cclip_weights(f64(G), f64(alpha), f64(c0), int(iters), t)
+        return c, info[0], info[1].to(torch.int32), info[2].to(torch.int32)
+    return composite.cclip_weights(G, alpha.to(G.device), c0.to(G.device), int(iters), t)
+
+
+def anchored_rows(U: torch.Tensor, c: torch.Tensor, anchor: torch.Tensor) -> torch.Tensor:
+    """anchor + sum_{j: c_j != 0} c_j (U_j - anchor) with fp64 weights on the rows' device (``k_anchored_rows``)."""
+    if _dev(U):
+        return native().anchored_rows(U.to(torch.float32).contiguous(),
+                                      c.to(device=U.device, dtype=torch.float64).contiguous(),
+                                      anchor.to(device=U.device, dtype=torch.float32).contiguous())
+    return composite.anchored_rows(U, c, anchor)
+
+
 def centred_gram(U: torch.Tensor) -> torch.Tensor:
     """n x n Gram of the rows centred on their mean (fp64).  Device, n <= 64: the fp64-MFMA Gram pass of ``agg.hip``
     (rows centred on one of them, then double-centred) instead of a generic fp64 GEMM with M = N = n and

@@ -285,6 +285,56 @@ def centred_gram(U: torch.Tensor) -> torch.Tensor:
     return Xc @ Xc.t()
 
 
+def gram_anchored(U: torch.Tensor, anchor: torch.Tensor) -> torch.Tensor:
+    """n x n Gram of the rows about an external centre, <U_i - anchor, U_j - anchor> (fp64; ``k_gram_f64`` with an
+    anchor on the device)."""
+    Y = U.double() - anchor.double()[None, :]
+    return Y @ Y.t()
+
+
+def cclip_weights(G: torch.Tensor, alpha: torch.Tensor, c0: torch.Tensor, iters: int, tau: float):
+    """Centred clipping in Gram space (``k_cclip_weights``; rule text in docs/PARITY.md): ``iters`` times
+    d_i^2 = max(0, G_ii - 2 (G c)_i + c^T G c), s_i = 1 when d_i <= tau else tau / d_i, c <- (1 - S) c + alpha s with
+    S = sum alpha s, from c = c0.  ``tau`` <= 0: the lower median (sorted position (m - 1) // 2) of the m finite rows'
+    d_i of the first iteration.  A row whose G_ii is not finite has s = 0 and c = 0 and is left out of every sum and
+    of the median; alpha is not renormalised.  -> (c [n] fp64, tau, rows with s < 1 in the last iteration, finite
+    rows), the last three 0-d tensors.  Tensor ops only (no host read), so it also serves device tensors beyond the
+    kernel's 64 rows."""
+    G, a, c = G.double(), alpha.double(), c0.double()
+    n = G.shape[0]
+    diag = G.diagonal()
+    fin = torch.isfinite(diag)
+    zero = torch.zeros((), dtype=torch.float64, device=G.device)
+    Gf = torch.where(fin[:, None] & fin[None, :], G, zero)  # (a skipped row or column adds nothing)
+    diag = torch.where(fin, diag, zero)
+    a = torch.where(fin, a, zero)
+    c = torch.where(fin, c, zero)
+    m = fin.sum()
+    t = torch.full((), float(tau), dtype=torch.float64, device=G.device)
+    clipped = torch.zeros((), dtype=torch.int64, device=G.device)
+    for it in range(int(iters)):
+        gc = (Gf * c[None, :]).sum(dim=1)  # (row by row in one order: identical rows get identical bits)
+        d = (diag - 2.0 * gc + (c * gc).sum()).clamp_min(0.0).sqrt()
+        if it == 0 and not float(tau) > 0.0:
+            key = torch.sort(torch.where(fin, d, torch.full_like(d, float("inf")))).values
+            t = torch.where(m > 0, key.gather(0, ((m - 1) // 2).clamp_min(0).reshape(1))[0], zero)
+        s = torch.where(fin, torch.where(d <= t, torch.ones_like(d), t / d), zero)  # (d > t >= 0 where divided)
+        c = torch.where(fin, (1.0 - (a * s).sum()) * c + a * s, zero)
+        clipped = (fin & (s < 1.0)).sum()
+    return c, t, clipped, m
+
+
+def anchored_rows(U: torch.Tensor, c: torch.Tensor, anchor: torch.Tensor) -> torch.Tensor:
+    """anchor + sum_{j: c_j != 0} c_j (U_j - anchor), the differences and the sum in fp64, rows in ascending order
+    (``k_anchored_rows``).  A row with c_j == 0 is left out, not multiplied by zero."""
+    g = anchor.double()
+    c = c.to(device=U.device, dtype=torch.float64)
+    acc = torch.zeros_like(g)
+    for j in range(U.shape[0]):
+        acc = acc + torch.where(c[j] != 0, c[j] * (U[j].double() - g), torch.zeros_like(g))
+    return (g + acc).to(U.dtype)
+
+
 def top_pc(G: torch.Tensor) -> torch.Tensor:
     """First principal-component scores v sqrt(lambda) from the centred Gram (``k_top_pc``, up to the sign)."""
     ev, V = torch.linalg.eigh(G)

@@ -249,6 +249,63 @@ std::vector<torch::Tensor> geomed_weights(torch::Tensor G, torch::Tensor alpha, 
   return {w, info};
 }
 
+// centred clipping (agg.cclip).  gram_anchored: U [K <= 64, P] fp32, anchor [P] fp32 -> the Gram [K, K] fp64 of the rows
+// about the anchor (one fp64-MFMA pass)
+torch::Tensor gram_anchored(torch::Tensor U, torch::Tensor anchor) {
+  check_dev(U, "U", torch::kFloat32);
+  check_dev(anchor, "anchor", torch::kFloat32);
+  TORCH_CHECK(U.dim() == 2 && U.size(0) >= 1 && U.size(0) <= 64 && U.size(1) >= 1, "gram_anchored: U [K <= 64, P >= 1]");
+  const int K = U.size(0);
+  const long P = U.size(1);
+  TORCH_CHECK(anchor.dim() == 1 && anchor.size(0) == P && anchor.device() == U.device(),
+              "gram_anchored: anchor [P] on U's device (got ", anchor.numel(), " values for P = ", P, ")");
+  auto gram = torch::zeros({K, K}, U.options().dtype(torch::kFloat64));
+  auto scratch = torch::empty({(long)afl_gram_partials(K, P)}, gram.options());
+  TORCH_CHECK(afl_gram_anchored(U.data_ptr<float>(), K, P, anchor.data_ptr<float>(), scratch.data_ptr<double>(),
+                                gram.data_ptr<double>(), cur()) == 0, "gram_anchored launch failed");
+  AFL_CHECK_LAUNCH();
+  return gram;
+}
+
+// cclip_weights: G [n, n], alpha / c0 [n] fp64, tau <= 0 = auto -> (c [n] fp64, info [3] fp64 {tau, clipped, finite})
+std::vector<torch::Tensor> cclip_weights(torch::Tensor G, torch::Tensor alpha, torch::Tensor c0, int64_t iters,
+                                         double tau) {
+  check_dev(G, "G", torch::kFloat64);
+  check_dev(alpha, "alpha", torch::kFloat64);
+  check_dev(c0, "c0", torch::kFloat64);
+  const int64_t n = G.size(0);
+  TORCH_CHECK(G.dim() == 2 && G.size(1) == n && alpha.numel() == n && c0.numel() == n && n >= 1 && n <= 64,
+              "cclip_weights: G [n, n], alpha [n], c0 [n], n <= 64");
+  TORCH_CHECK(alpha.device() == G.device() && c0.device() == G.device(), "cclip_weights: every tensor on G's device");
+  TORCH_CHECK(iters >= 1 && iters <= 65535 && tau == tau, "cclip_weights: 1 <= iters <= 65535 and tau a number (got ",
+              iters, ", ", tau, ")");
+  auto c = torch::zeros({n}, G.options());
+  auto info = torch::zeros({3}, G.options());
+  TORCH_CHECK(afl_cclip_weights(G.data_ptr<double>(), alpha.data_ptr<double>(), c0.data_ptr<double>(), (int)n,
+                                (int)iters, tau, c.data_ptr<double>(), info.data_ptr<double>(), cur()) == 0,
+              "cclip_weights launch failed");
+  AFL_CHECK_LAUNCH();
+  return {c, info};
+}
+
+// anchored_rows: U [N, P] fp32, c [N] fp64 (device), anchor [P] fp32 -> anchor + sum_{c_j != 0} c_j (U_j - anchor) [P]
+torch::Tensor anchored_rows(torch::Tensor U, torch::Tensor c, torch::Tensor anchor) {
+  check_dev(U, "U", torch::kFloat32);
+  check_dev(c, "c", torch::kFloat64);
+  check_dev(anchor, "anchor", torch::kFloat32);
+  TORCH_CHECK(U.dim() == 2 && U.size(0) >= 1 && U.size(0) <= INT_MAX && U.size(1) >= 1, "anchored_rows: U [N, P]");
+  const int N = U.size(0);
+  const long P = U.size(1);
+  TORCH_CHECK(c.numel() == N && anchor.dim() == 1 && anchor.size(0) == P, "anchored_rows: c [N], anchor [P] (got ",
+              c.numel(), " and ", anchor.numel(), " for N = ", N, ", P = ", P, ")");
+  TORCH_CHECK(c.device() == U.device() && anchor.device() == U.device(), "anchored_rows: every tensor on U's device");
+  auto out = torch::empty({P}, U.options());
+  TORCH_CHECK(afl_anchored_rows(U.data_ptr<float>(), c.data_ptr<double>(), N, P, anchor.data_ptr<float>(),
+                                out.data_ptr<float>(), cur()) == 0, "anchored_rows launch failed");
+  AFL_CHECK_LAUNCH();
+  return out;
+}
+
 // Gram matrix of the rows centred on the MEAN row (PCA of the updates: agg.fltracer / agg.gmm), through the same
 // fp64-MFMA pass (H: the Gram of the rows centred on the pass's final centre row, the scratch tail) followed by the
 // double centring C = H - rowmean - colmean + mean, which does not depend on the centre beyond rounding
@@ -954,6 +1011,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dnc_run", &dnc_run);
   m.def("bulyan_coord", &bulyan_coord);
   m.def("geomed_weights", &geomed_weights);
+  m.def("gram_anchored", &gram_anchored);
+  m.def("cclip_weights", &cclip_weights);
+  m.def("anchored_rows", &anchored_rows);
   m.def("fxsum_test", &fxsum_test);
   m.def("tf2_wgs_per_client", &afl_tf2_wgs_per_client);
   m.def("gram_centred", &gram_centred);

@@ -476,6 +476,15 @@ int afl_bulyan_coord(const float* U, int N, long P, const int* sel, int theta, i
 // simplex -> w [n] fp64, info = {iterations, objective}
 int afl_geomed_weights(const double* G, const double* alpha, int n, int iters, double nu, double* w, double* info,
                        hipStream_t s);
+// centred clipping (docs/PARITY.md).  afl_gram_anchored: gram [K][K] = <U_i - anchor, U_j - anchor> on the fp64-MFMA
+// Gram pass (K <= 64; partial: afl_gram_partials(K, P) doubles).  afl_cclip_weights (agg.hip k_cclip_weights): G
+// [n][n], alpha / c0 [n] fp64, ``iters`` clipping iterations with radius tau (<= 0: the lower median of the first
+// iteration's finite distances) -> c [n], info = {tau, rows clipped in the last iteration, finite rows}.
+// afl_anchored_rows: out = g + sum_{j: c_j != 0} c_j (U_j - g), c on the device.
+int afl_gram_anchored(const float* U, int K, long P, const float* anchor, double* partial, double* gram, hipStream_t s);
+int afl_cclip_weights(const double* G, const double* alpha, const double* c0, int n, int iters, double tau, double* c,
+                      double* info, hipStream_t s);
+int afl_anchored_rows(const float* U, const double* c, int N, long P, const float* g, float* out, hipStream_t s);
 // Divide-and-Conquer (DnC, docs/PARITY.md) on U [K <= 64][P] fp32.  afl_dnc_gram (agg.hip k_dnc_gram): for each of
 // ``iters`` iterations the tile-pair partials of the Gram of the rows centred on row 0, over the b keyed columns of
 // that iteration (all P in natural order when b >= P) -> partial, afl_dnc_partials(K, P, b, iters) doubles.

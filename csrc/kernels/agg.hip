@@ -14,6 +14,8 @@
 //   krum_select     Multi-Krum ranking / Bulyan iterated selection on the distance matrix (beyond the reference)
 //   bulyan_coord    Bulyan's mean of the beta values closest to the column median, over selected rows
 //   geomed_weights  smoothed Weiszfeld (geometric median, RFA) in Gram space
+//   cclip_weights   centred clipping in Gram space (anchored Gram: gram_f64 about the previous global model)
+//   anchored_rows   out = g + sum_i c_i (U_i - g) (fp64 weights, fp64 accumulate): centred clipping's row pass
 //   dnc_gram        DnC: fp64-MFMA Grams over keyed random column subsets, all iterations in one launch
 //   dnc_select      DnC: top eigenpair, scores, ranked drop, mask intersection and weights, one wave
 //
@@ -158,19 +160,27 @@ int afl_pair_sqdist(const float* G, int K, long P, double* partial, double* D, h
 // 16 columns per step: lane l loads 4 consecutive columns of row (tile*16 + (l & 15)), column group l >> 4,
 // and issues 4 MFMAs per tile pair (element q of the 4 = MFMA q's k = l >> 4: the 16 columns are summed in a
 // fixed, data-independent order).  f64 C/D layout: acc[r] = C[(l >> 4) + 4r][l & 15].
+// An external centre (``anchor`` [P], afl_gram_anchored: centred clipping's previous global model) replaces the
+// centre row: y_i = G_i - anchor, one pass, and k_gram_reduce's ``gram`` is then the raw Gram Y Y^T about it.  Error
+// model of that form:
+//     err(G_ij) <~ eps64 * |y_i| |y_j|
+// and a distance formed from it, d_i^2 = G_ii - 2 (G c)_i + c^T G c to a point v = anchor + sum_j c_j y_j, loses
+// log2(G_ii / d_i^2) bits when v comes close to x_i.  A non-finite row poisons its own row and column of the Gram
+// only (an MFMA output element reads one row of each operand).
 constexpr int GR_CH = 1024;
 typedef double d4v __attribute__((ext_vector_type(4)));
 
 template <int T>
 __global__ void __launch_bounds__(256) k_gram_f64(const float* __restrict__ G, int K, long P,
-                                                  const int* __restrict__ centre, double* __restrict__ partial) {
+                                                  const int* __restrict__ centre, double* __restrict__ partial,
+                                                  const float* __restrict__ anchor) {
   constexpr int NP = T * (T + 1) / 2;
   int crow = 0;  // pass 1 (centre == nullptr): row 0; pass 2: the picked row, nothing to do when that is row 0
   if (centre != nullptr) {
     crow = *centre;
     if (crow <= 0 || crow >= K) return;  // (block-uniform)
   }
-  const float* Gc = G + (long)crow * P;
+  const float* Gc = anchor != nullptr ? anchor : G + (long)crow * P;  // (an anchor comes with centre == nullptr)
   __shared__ double red[4][NP * 256];  // NP <= 10 tile pairs x 16 x 16
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r16 = lane & 15, grp = lane >> 4;
@@ -270,7 +280,7 @@ __device__ void gram_pick_centre(const double* __restrict__ V, double* __restric
 
 // sum the block partials in block order, then D2 = g_ii + g_jj - 2 g_ij (clamped at 0), symmetric, zero diagonal.
 // Pass 1 (centre == nullptr) then picks pass 2's centre into *pick (when given); pass 2 (centre as in k_gram_f64)
-// returns at once when the picked row is row 0.
+// returns at once when the picked row is row 0.  D == nullptr (the anchored Gram): the Gram alone.
 __global__ void __launch_bounds__(256) k_gram_reduce(const double* __restrict__ partial, int nb, int K, int T,
                                                      const int* __restrict__ centre, double* __restrict__ gram,
                                                      double* __restrict__ D, int* __restrict__ pick) {
@@ -293,6 +303,7 @@ __global__ void __launch_bounds__(256) k_gram_reduce(const double* __restrict__ 
       gram[j * K + i] = a;
     }
   }
+  if (D == nullptr) return;  // (uniform)
   __syncthreads();
   for (int e = threadIdx.x; e < K * K; e += 256) {
     const int i = e / K, j = e % K;
@@ -315,12 +326,12 @@ int afl_gram_partials(int K, long P) {
 }
 
 static void gram_pass(const float* G, int K, long P, int T, int nb, const int* centre, double* partial, double* gram,
-                      double* D, int* pick, hipStream_t s) {
+                      double* D, int* pick, hipStream_t s, const float* anchor = nullptr) {
   switch (T) {
-    case 1: hipLaunchKernelGGL(k_gram_f64<1>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial); break;
-    case 2: hipLaunchKernelGGL(k_gram_f64<2>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial); break;
-    case 3: hipLaunchKernelGGL(k_gram_f64<3>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial); break;
-    default: hipLaunchKernelGGL(k_gram_f64<4>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial); break;
+    case 1: hipLaunchKernelGGL(k_gram_f64<1>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial, anchor); break;
+    case 2: hipLaunchKernelGGL(k_gram_f64<2>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial, anchor); break;
+    case 3: hipLaunchKernelGGL(k_gram_f64<3>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial, anchor); break;
+    default: hipLaunchKernelGGL(k_gram_f64<4>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial, anchor); break;
   }
   hipLaunchKernelGGL(k_gram_reduce, dim3(1), dim3(256), 0, s, partial, nb, K, T, centre, gram, D, pick);
 }
@@ -334,6 +345,16 @@ int afl_pair_sqdist_gram(const float* G, int K, long P, double* partial, double*
   // (K <= 2: every row is as central as row 0, one pass)
   gram_pass(G, K, P, T, nb, nullptr, partial, gram, D, K > 2 ? centre : nullptr, s);
   if (K > 2) gram_pass(G, K, P, T, nb, centre, partial, gram, D, nullptr, s);
+  return (int)hipGetLastError();
+}
+
+// the raw Gram of the rows about an external centre: gram[i][j] = <U_i - anchor, U_j - anchor>, one pass; ``partial``
+// as for afl_pair_sqdist_gram (afl_gram_partials doubles cover it)
+int afl_gram_anchored(const float* U, int K, long P, const float* anchor, double* partial, double* gram,
+                      hipStream_t s) {
+  if (K < 1 || K > GR_MAXK || P < 1 || anchor == nullptr) return (int)hipErrorInvalidValue;
+  const int T = (K + 15) / 16, nb = afl_cdiv(P, GR_CH);
+  gram_pass(U, K, P, T, nb, nullptr, partial, gram, nullptr, nullptr, s, anchor);
   return (int)hipGetLastError();
 }
 
@@ -1512,5 +1533,100 @@ int afl_geomed_weights(const double* G, const double* alpha, int n, int iters, d
                        hipStream_t s) {
   if (n < 1 || n > GMM_MAXN || iters < 1 || !(nu > 0.0)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_geomed_weights, dim3(1), dim3(64), 0, s, G, alpha, n, iters, nu, w, info);
+  return (int)hipGetLastError();
+}
+
+// ============================================================================ cclip_weights
+// Centred clipping (Karimireddy, He & Jaggi, ICML 2021; rule text in docs/PARITY.md) of n <= 64 rows in Gram space.
+// The iterate is v = g + sum_j c_j y_j (G the Gram of y_i = x_i - g about the centre g, c0 = 0) or v = sum_j c_j x_j
+// (G the mean-centred Gram, c0 = alpha, sum c = 1 kept by the update); either way
+//     d_i^2 = max(0, G_ii - 2 (G c)_i + c^T G c),  s_i = d_i <= tau ? 1 : tau / d_i,  c <- (1 - S) c + alpha s,
+// S = sum_i alpha_i s_i, exactly ``iters`` times.  tau <= 0 on entry means auto: the lower median (sorted position
+// (m - 1) / 2) of the m finite rows' d_i of iteration 0, by rank counting with ties ranked by row (exactly one row
+// has the wanted rank), kept for every iteration and never read back.  A row whose G_ii is not finite (a faulted
+// client's NaN row) has s = 0 and c = 0 exactly and is skipped, not multiplied by zero, in G c, c^T G c, S and the
+// median; alpha is not renormalised.  One wave, lane i owns row i of G in LDS (row stride n_max + 1): G c is a per-lane
+// dot product in column order, the sums are xor butterflies that leave the same bits on every lane.
+// info = {tau, rows with s < 1 in the last iteration, finite rows}.
+__global__ void __launch_bounds__(64) k_cclip_weights(const double* __restrict__ G, const double* __restrict__ alpha,
+                                                      const double* __restrict__ c0, int n, int iters, double tau_in,
+                                                      double* __restrict__ c, double* __restrict__ info) {
+  __shared__ double A[GMM_MAXN * KS_LD], cb[GMM_MAXN], db[GMM_MAXN], tau_s;
+  const int i = threadIdx.x;
+  for (int e = i; e < n * n; e += 64) {
+    const int r = e / n, cc = e - r * n;
+    A[r * KS_LD + cc] = G[e];
+  }
+  __syncthreads();
+  const double gii = i < n ? A[i * KS_LD + i] : 0.0;
+  const bool fin = i < n && gram_finite(gii);
+  const unsigned long long fm = __ballot(fin);
+  const int m = __popcll(fm);
+  const double al = fin ? alpha[i] : 0.0;
+  double ci = fin ? c0[i] : 0.0, tau = tau_in;
+  int clipped = 0;
+  for (int it = 0; it < iters; ++it) {
+    cb[i] = ci;
+    __syncthreads();
+    double gc = 0.0;
+    if (fin)
+      for (int j = 0; j < n; ++j)
+        if ((fm >> j) & 1ull) gc += A[i * KS_LD + j] * cb[j];
+    const double q = wave_sum(fin ? ci * gc : 0.0);
+    const double d2 = gii - 2.0 * gc + q;
+    const double d = fin ? sqrt(d2 > 0.0 ? d2 : 0.0) : INFINITY;
+    if (it == 0 && !(tau_in > 0.0)) {  // auto (uniform)
+      db[i] = d;
+      if (i == 0) tau_s = 0.0;  // (no finite row)
+      __syncthreads();
+      int rank = 0;
+      if (fin)
+        for (int l = 0; l < n; ++l)
+          rank += (((fm >> l) & 1ull) && (db[l] < d || (db[l] == d && l < i))) ? 1 : 0;
+      if (fin && rank == (m - 1) / 2) tau_s = d;
+      __syncthreads();
+      tau = tau_s;
+    }
+    const double s = fin ? (d <= tau ? 1.0 : tau / d) : 0.0;  // (d > tau >= 0: no division by zero)
+    const double S = wave_sum(al * s);
+    ci = fin ? (1.0 - S) * ci + al * s : 0.0;
+    clipped = __popcll(__ballot(fin && s < 1.0));
+    __syncthreads();  // (cb is rewritten by the next iteration)
+  }
+  if (i < n) c[i] = ci;
+  if (i == 0) {
+    info[0] = tau;
+    info[1] = (double)clipped;
+    info[2] = (double)m;
+  }
+}
+
+int afl_cclip_weights(const double* G, const double* alpha, const double* c0, int n, int iters, double tau, double* c,
+                      double* info, hipStream_t s) {
+  if (n < 1 || n > GMM_MAXN || iters < 1 || tau != tau) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_cclip_weights, dim3(1), dim3(64), 0, s, G, alpha, c0, n, iters, tau, c, info);
+  return (int)hipGetLastError();
+}
+
+// ============================================================================ anchored rows
+// out = (float)(g + sum_{j: c_j != 0} c_j (U_j - g)): centred clipping's result about the centre g, the weights read
+// from the device; one column per thread, rows in ascending order, differences and sum in fp64.  A row with c_j == 0
+// (a non-finite row's weight) is not read into the sum.
+__global__ void __launch_bounds__(256) k_anchored_rows(const float* __restrict__ U, const double* __restrict__ c, int N,
+                                                       long P, const float* __restrict__ g, float* __restrict__ out) {
+  long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  const double gp = (double)g[p];
+  double acc = 0.0;
+  for (int j = 0; j < N; ++j) {
+    const double cj = c[j];
+    if (cj != 0.0) acc += cj * ((double)U[(long)j * P + p] - gp);
+  }
+  out[p] = (float)(gp + acc);
+}
+
+int afl_anchored_rows(const float* U, const double* c, int N, long P, const float* g, float* out, hipStream_t s) {
+  if (N < 1 || P < 1) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_anchored_rows, dim3(afl_cdiv(P, 256)), dim3(256), 0, s, U, c, N, P, g, out);
   return (int)hipGetLastError();
 }

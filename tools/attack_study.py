@@ -47,7 +47,8 @@ def cells(spec: str):
 
 
 def run_cell(mode: str, attack: str, device: str, rounds: int, threads: int = 0, genuine_rate: float = 0.5,
-             distance: str = "spectral", seed: int = 7, tau: float = None, attackers: int = 3) -> dict:
+             distance: str = "spectral", seed: int = 7, tau: float = None, attackers: int = 3,
+             engine_set: dict = None) -> dict:
     import torch
 
     if threads:
@@ -64,7 +65,7 @@ def run_cell(mode: str, attack: str, device: str, rounds: int, threads: int = 0,
         "learning": {"epoch": 2, "batch-size": 128, "learning-rate": 0.004},
         "data": {"synthetic": True, "train-size": 20000, "test-size": 3000},
         "engine": {"checkpoint-dir": tmp, "trainer": "auto" if device.startswith("cuda") else "oracle", "seed": seed,
-                   "max-retries": 5, "distance": distance},
+                   "max-retries": 5, "distance": distance, **(engine_set or {})},
         "log_path": tmp,
     }
     cfg = from_dict(d)
@@ -86,8 +87,8 @@ def run_cell(mode: str, attack: str, device: str, rounds: int, threads: int = 0,
     return {"device": "gpu" if device.startswith("cuda") else "cpu", "mode": mode, "attack": attack,
             "genuine_rate": genuine_rate, "distance": distance, "seed": seed,
             "tau": next((a.tau for a in atk.values()), 1.0 if tau is None else tau),
-            "attackers": len(atk), "attack_args": args, "rounds": len(ok), "failed_rounds": len(hist) - len(ok),
-            "stalled": stalled,
+            "attackers": len(atk), "attack_args": args, "engine_set": engine_set or {}, "rounds": len(ok),
+            "failed_rounds": len(hist) - len(ok), "stalled": stalled,
             "auc": [round(r["metric"], 5) for r in ok], "final_auc": round(ok[-1]["metric"], 5) if ok else None,
             "attack_gamma": [round(r["attack"]["gamma"], 4) for r in ok if "attack" in r and "gamma" in r["attack"]],
             # last ACCEPTED γ per attacking round (0: every tried γ was rejected)
@@ -98,8 +99,8 @@ def run_cell(mode: str, attack: str, device: str, rounds: int, threads: int = 0,
 
 
 def _worker(args):
-    mode, attack, device, rounds, threads, gr, dist, seed, tau, na = args
-    return run_cell(mode, attack, device, rounds, threads, gr, dist, seed, tau, na)
+    mode, attack, device, rounds, threads, gr, dist, seed, tau, na, es = args
+    return run_cell(mode, attack, device, rounds, threads, gr, dist, seed, tau, na, es)
 
 
 def main() -> int:
@@ -115,7 +116,11 @@ def main() -> int:
                     help="bisection stop gap (default: the attack's own, 1.0 as the reference, 0.02 for the AGR modes)")
     ap.add_argument("--attackers", type=int, default=3, help="attacking clients (the last N of 8)")
     ap.add_argument("--seeds", default="7", help="comma-separated run seeds (engine seed; server random-seed = seed - 6)")
+    ap.add_argument("--engine-set", default="", help="engine keys for every cell, key=value,... (e.g. cclip-iters=1)")
     args = ap.parse_args()
+    import yaml
+
+    engine_set = {k: yaml.safe_load(v) for k, v in (kv.split("=", 1) for kv in args.engine_set.split(",") if kv)}
     seeds = [int(x) for x in args.seeds.split(",")]
     todo = [(m, a, sd) for m, a in cells(args.cells) for sd in seeds]
     with open(args.out, "a") as fh:
@@ -125,7 +130,7 @@ def main() -> int:
             threads = max(1, (os.cpu_count() or 8) // args.jobs)
             with mp.get_context("spawn").Pool(args.jobs) as pool:
                 for res in pool.imap_unordered(_worker, [(m, a, args.device, args.rounds, threads, args.genuine_rate,
-                                                                   args.distance, sd, args.tau, args.attackers)
+                                                                   args.distance, sd, args.tau, args.attackers, engine_set)
                                                                   for m, a, sd in todo]):
                     fh.write(json.dumps(res) + "\n")
                     fh.flush()
@@ -133,7 +138,7 @@ def main() -> int:
         else:
             for m, a, sd in todo:
                 res = run_cell(m, a, args.device, args.rounds, 0, args.genuine_rate, args.distance, sd, args.tau,
-                               args.attackers)
+                               args.attackers, engine_set)
                 fh.write(json.dumps(res) + "\n")
                 fh.flush()
                 print(res["mode"], res["attack"], res["final_auc"], res["seconds"], flush=True)
