@@ -28,6 +28,7 @@ from typing import Dict, Optional, Union
 import torch
 
 from .. import ops
+from ..config import KNOB  # (a rule knob's default and check: stated once, in config.RULE_KNOBS)
 from ..ops.composite import gmm_filter_ref  # noqa: F401  (the kernel's host mirror: tools and tests import it here)
 
 
@@ -66,9 +67,9 @@ def host_info(info: Dict) -> Dict:
     return out
 
 
-def _device_weights(sizes: torch.Tensor, device) -> torch.Tensor:
-    """Host sizes -> a device fp64 vector without a synchronising pageable copy."""
-    s = sizes.to(torch.float64)
+def _device_weights(sizes: Optional[torch.Tensor], device, n: int = 0) -> torch.Tensor:
+    """Host sizes (None: n ones) -> a device fp64 vector without a synchronising pageable copy."""
+    s = torch.ones(n, dtype=torch.float64) if sizes is None else sizes.to(torch.float64)
     if torch.device(device).type == "cuda" and s.device.type == "cpu":
         s = s.pin_memory().to(device, non_blocking=True)
     return s.to(device)
@@ -106,34 +107,31 @@ def krum(U: torch.Tensor, sizes=None, f_rate: float = 0.0, **_) -> AggResult:
     return AggResult(U.index_select(0, sel.reshape(1))[0], True, {"selected": sel, "f": f, "scores": scores})
 
 
-def byzantine_count(n: int, byz_f="auto", per_f: int = 4, rule: str = "bulyan") -> int:
+def byzantine_count(n: int, byz_f=KNOB["byz_f"].default, per_f: int = 4, rule: str = "bulyan") -> int:
     """The assumed number f of Byzantine rows (engine ``byz-f``).  ``auto``: max(0, (n - 3) // 4), the largest f
     Bulyan admits.  An explicit f >= 1 must leave n >= per_f * f + 3 rows (2 f + 3 for Multi-Krum, 4 f + 3 for
     Bulyan); f = 0 claims no tolerance and is admitted for any n."""
-    if byz_f is None or byz_f == "auto":
+    f = KNOB["byz_f"].check(byz_f, coerce=True)
+    if f == "auto":
         return max(0, (n - 3) // 4)
-    f = int(byz_f)
-    if f < 0:
-        raise ValueError(f"byz-f must be 'auto' or an integer >= 0 (got {byz_f}).")
     if f > 0 and n < per_f * f + 3:
         raise ValueError(f"Too few clients for {rule} with byz-f = {f}: n = {n}, needs n >= {per_f} f + 3 = "
                          f"{per_f * f + 3}.")
     return f
 
 
-def multi_krum(U: torch.Tensor, sizes=None, byz_f="auto", **_) -> AggResult:
+def multi_krum(U: torch.Tensor, sizes=None, byz_f=KNOB["byz_f"].default, **_) -> AggResult:
     """Multi-Krum (Blanchard et al., NeurIPS 2017; beyond the reference, whose ``krum`` keeps f = 0, A-11): Krum scores
     with k = max(n - f - 2, 1) neighbours on all rows, the n - f rows with the smallest (score, index), their
     size-weighted mean.  One ``k_krum_select`` launch on the Gram-form distances; no host read."""
     n = U.shape[0]
     f = byzantine_count(n, byz_f, 2, "multi_krum")
     _, keep, scores = ops.krum_select(ops.pairwise_sqdist(U), f, n - f, False)
-    w = torch.ones(n, dtype=torch.float64) if sizes is None else sizes
-    w = _device_weights(w, U.device) * keep.double()
+    w = _device_weights(sizes, U.device, n) * keep.double()
     return AggResult(ops.weighted_rows(U, w / w.sum()), True, {"selected": keep, "f": f, "scores": scores})
 
 
-def bulyan(U: torch.Tensor, sizes=None, byz_f="auto", **_) -> AggResult:
+def bulyan(U: torch.Tensor, sizes=None, byz_f=KNOB["byz_f"].default, **_) -> AggResult:
     """Bulyan (El Mhamdi et al., ICML 2018; beyond the reference): theta = n - 2 f rows by iterated Krum (re-scored on
     the rows still active before every pick), then per column the unweighted mean of the beta = theta - 2 f values
     closest to the lower median of the selected ones.  Two launches after the distances (``k_krum_select``,
@@ -145,19 +143,19 @@ def bulyan(U: torch.Tensor, sizes=None, byz_f="auto", **_) -> AggResult:
     return AggResult(ops.bulyan_coord(U, sel, theta - 2 * f), True, {"selected": keep, "f": f, "scores": scores})
 
 
-def geomed(U: torch.Tensor, sizes=None, geomed_iters: int = 100, geomed_nu: float = 1e-6, **_) -> AggResult:
+def geomed(U: torch.Tensor, sizes=None, geomed_iters: int = KNOB["geomed_iters"].default,
+           geomed_nu: float = KNOB["geomed_nu"].default, **_) -> AggResult:
     """Geometric median by the smoothed Weiszfeld iteration of RFA (Pillutla et al., 2022; beyond the reference),
     weighted by alpha = sizes / sum sizes, run in Gram space on the n x n centred Gram (``k_geomed_weights``): the
     rows are read by the Gram pass and by the final ``weighted_rows`` only.  No host read."""
     n = U.shape[0]
-    a = torch.ones(n, dtype=torch.float64) if sizes is None else sizes
-    a = _device_weights(a, U.device)
+    a = _device_weights(sizes, U.device, n)
     w, iters, obj = ops.geomed_weights(ops.centred_gram(U), a / a.sum(), int(geomed_iters), float(geomed_nu))
     return AggResult(ops.weighted_rows(U, w), True, {"weights": w, "iters": iters, "objective": obj})
 
 
-def cclip(U: torch.Tensor, sizes=None, centre: Optional[torch.Tensor] = None, cclip_iters: int = 3, cclip_tau="auto",
-          **_) -> AggResult:
+def cclip(U: torch.Tensor, sizes=None, centre: Optional[torch.Tensor] = None,
+          cclip_iters: int = KNOB["cclip_iters"].default, cclip_tau=KNOB["cclip_tau"].default, **_) -> AggResult:
     """Centred clipping (Karimireddy, He & Jaggi, ICML 2021; one iteration = norm bounding, Sun et al. 2019; beyond the
     reference, rule text in docs/PARITY.md): from v = ``centre`` (the global model the round started from; the
     alpha-weighted mean of the rows when None), ``cclip_iters`` times v <- v + sum_i alpha_i s_i (x_i - v) with
@@ -167,27 +165,22 @@ def cclip(U: torch.Tensor, sizes=None, centre: Optional[torch.Tensor] = None, cc
     centre a non-finite row is left out (its alpha not redistributed) and the result is the centre when no row is
     finite; without one it makes the result non-finite, as FedAvg's is.  Always a new tensor."""
     n = U.shape[0]
-    iters = int(cclip_iters)
-    auto = cclip_tau is None or (isinstance(cclip_tau, str) and cclip_tau == "auto")
-    tau = 0.0 if auto else float(cclip_tau)
-    if iters < 1 or not (auto or tau > 0):
-        raise ValueError(f"cclip needs cclip-iters >= 1 and cclip-tau 'auto' or > 0 (got {cclip_iters}, {cclip_tau}).")
-    a = torch.ones(n, dtype=torch.float64) if sizes is None else sizes
-    a = _device_weights(a, U.device)
+    iters, tau = (KNOB[k].check(v, coerce=True) for k, v in (("cclip_iters", cclip_iters), ("cclip_tau", cclip_tau)))
+    a = _device_weights(sizes, U.device, n)
     alpha = a / a.sum()
     if centre is None:
-        c, t, clipped, _ = ops.cclip_weights(ops.centred_gram(U), alpha, alpha, iters, "auto" if auto else tau)
+        c, t, clipped, _ = ops.cclip_weights(ops.centred_gram(U), alpha, alpha, iters, tau)
         out = ops.weighted_rows(U, c)
     else:
         g = centre.to(device=U.device, dtype=torch.float32)
-        c, t, clipped, _ = ops.cclip_weights(ops.gram_anchored(U, g), alpha, torch.zeros_like(alpha), iters,
-                                             "auto" if auto else tau)
+        c, t, clipped, _ = ops.cclip_weights(ops.gram_anchored(U, g), alpha, torch.zeros_like(alpha), iters, tau)
         out = ops.anchored_rows(U, c, g)
     return AggResult(out, True, {"weights": c, "tau": t, "clipped": clipped, "iters": iters})
 
 
-def dnc(U: torch.Tensor, sizes=None, byz_f="auto", dnc_iters: int = 1, dnc_sub_dim: int = 10000, dnc_c: float = 1.0,
-        seed: int = 0, **_) -> AggResult:
+def dnc(U: torch.Tensor, sizes=None, byz_f=KNOB["byz_f"].default, dnc_iters: int = KNOB["dnc_iters"].default,
+        dnc_sub_dim: int = KNOB["dnc_sub_dim"].default, dnc_c: float = KNOB["dnc_c"].default, seed: int = 0,
+        **_) -> AggResult:
     """Divide-and-Conquer (Shejwalkar & Houmansadr, NDSS 2021; beyond the reference, rule text in docs/PARITY.md):
     ``dnc_iters`` times, the Gram of the rows on ``dnc_sub_dim`` keyed random columns (all of them in natural order
     when that is >= P), scores lambda_1 u_i^2 from its top eigenpair, the drop = min(ceil(c f), n - 1) rows with the
@@ -196,13 +189,10 @@ def dnc(U: torch.Tensor, sizes=None, byz_f="auto", dnc_iters: int = 1, dnc_sub_d
     no host read.  drop = 0 is FedAvg itself."""
     n = U.shape[0]
     f = byzantine_count(n, byz_f, 2, "dnc")
-    iters, b, c = int(dnc_iters), int(dnc_sub_dim), float(dnc_c)
-    if iters < 1 or b < 1 or not c > 0:
-        raise ValueError(f"dnc needs dnc-iters >= 1, dnc-sub-dim >= 1 and dnc-c > 0 (got {dnc_iters}, {dnc_sub_dim}, "
-                         f"{dnc_c}).")
+    iters, b, c = (KNOB[k].check(v, coerce=True)
+                   for k, v in (("dnc_iters", dnc_iters), ("dnc_sub_dim", dnc_sub_dim), ("dnc_c", dnc_c)))
     drop = min(math.ceil(c * f), n - 1)
-    s = torch.ones(n, dtype=torch.float64) if sizes is None else sizes
-    s = _device_weights(s, U.device)
+    s = _device_weights(sizes, U.device, n)
     keep, scores, w = ops.dnc_filter(U, b, iters, seed, drop, s)
     out = ops.fedavg(U, s) if drop == 0 else ops.weighted_rows(U, w)
     return AggResult(out, True, {"selected": keep, "f": f, "drop": drop, "scores": scores})

@@ -126,6 +126,55 @@ REFERENCE_DEFAULTS: Dict[str, Any] = {
                  "clip-grad-norm": 1.0},
 }
 
+
+@dataclass(frozen=True)
+class RuleKnob:
+    """One engine knob of a server rule: the ``engine:`` key, the keyword the rule receives, what it holds (``kind``
+    "int" >= ``lo``, unchecked when ``lo`` is None, or "number" > 0; ``auto``: or the string "auto") and the default.
+    Stated once, in RULE_KNOBS: the engine defaults, ``validate``, ``FLEngine._rule_args`` and the rules (``agg``)
+    read it."""
+    key: str
+    kw: str
+    kind: str
+    default: Any
+    lo: Optional[int] = None
+    auto: bool = False
+
+    def check(self, v, where: str = "", coerce: bool = False):
+        """-> ``v`` when admissible, else ValueError.  A bool never is; a string only as a "number" (YAML 1.1 reads
+        "1e-6", without a dot, as a string); NaN is not > 0.  ``coerce`` (the engine's keywords, a rule's own
+        arguments): None counts as "auto", any other value goes through ``int`` / ``float`` first."""
+        if self.auto and ((isinstance(v, str) and v == "auto") or (coerce and v is None)):
+            return "auto"
+        if coerce:
+            v = int(v) if self.kind == "int" else float(v)
+        if self.kind == "int" and self.lo is None:
+            return v
+        try:
+            ok = not isinstance(v, bool) and ((isinstance(v, int) and v >= self.lo) if self.kind == "int"
+                                              else float(v) > 0)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            what = f"an integer >= {self.lo}" if self.kind == "int" else "a number > 0"
+            what = "'auto' or " + what if self.auto else what
+            raise ValueError(f"{where}{self.key} must be {what} (got {v!r})")
+        return v
+
+
+RULE_KNOBS = (  # engine key, rule keyword, kind, default, lo, auto  (what each one means: the module docstring)
+    RuleKnob("gmm-rank", "gmm_rank", "int", 1),
+    RuleKnob("byz-f", "byz_f", "int", "auto", 0, True),
+    RuleKnob("geomed-iters", "geomed_iters", "int", 100, 1),
+    RuleKnob("geomed-nu", "geomed_nu", "number", 1e-6),
+    RuleKnob("dnc-iters", "dnc_iters", "int", 1, 1),
+    RuleKnob("dnc-sub-dim", "dnc_sub_dim", "int", 10000, 1),
+    RuleKnob("dnc-c", "dnc_c", "number", 1.0),
+    RuleKnob("cclip-iters", "cclip_iters", "int", 3, 1),
+    RuleKnob("cclip-tau", "cclip_tau", "number", "auto", None, True),
+)
+KNOB = {k.kw: k for k in RULE_KNOBS}
+
 EXTENSION_DEFAULTS: Dict[str, Any] = {
     "comm": {"backend": "auto", "address": "", "port": 29517, "clients-per-rank": 0, "one-shot-allgather": "auto",
              "fedavg-allreduce": "auto", "timeout-s": 600, "attackers": {}},
@@ -134,9 +183,8 @@ EXTENSION_DEFAULTS: Dict[str, Any] = {
     "engine": {"trainer": "auto", "distance": "spectral", "seed": 0, "metrics": "", "checkpoint-dir": ".",
                "async-checkpoint": True, "compat-hyper-resume": False, "compat-fltrust": False, "max-retries": 50, "trace": False,
                "phase-sync": False, "fault-inject": [], "save-state": False, "resume": False,
-               "speculative": True, "compat-har-train": False, "compat-fedavg-alias": False, "gmm-rank": 1,
-               "byz-f": "auto", "geomed-iters": 100, "geomed-nu": 1e-6, "dnc-iters": 1, "dnc-sub-dim": 10000,
-               "dnc-c": 1.0, "cclip-iters": 3, "cclip-tau": "auto"},
+               "speculative": True, "compat-har-train": False, "compat-fedavg-alias": False,
+               **{k.key: k.default for k in RULE_KNOBS}},
 }
 
 
@@ -299,38 +347,8 @@ class Config:
             raise ValueError("server.clients must be >= 1")
         if self.engine["distance"] not in ("spectral", "flat"):
             raise ValueError("engine.distance must be 'spectral' or 'flat'")
-        f = self.engine.get("byz-f", "auto")
-        if f != "auto" and (isinstance(f, bool) or not isinstance(f, int) or f < 0):
-            raise ValueError(f"engine.byz-f must be 'auto' or an integer >= 0 (got {f!r})")
-        it, nu = self.engine.get("geomed-iters", 100), self.engine.get("geomed-nu", 1e-6)
-        if isinstance(it, bool) or not isinstance(it, int) or it < 1:
-            raise ValueError(f"engine.geomed-iters must be an integer >= 1 (got {it!r})")
-        try:  # (YAML 1.1 reads "1e-6", without a dot, as a string)
-            nu_ok = not isinstance(nu, bool) and float(nu) > 0
-        except (TypeError, ValueError):
-            nu_ok = False
-        if not nu_ok:
-            raise ValueError(f"engine.geomed-nu must be a number > 0 (got {nu!r})")
-        for key, default in (("dnc-iters", 1), ("dnc-sub-dim", 10000)):
-            v = self.engine.get(key, default)
-            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
-                raise ValueError(f"engine.{key} must be an integer >= 1 (got {v!r})")
-        c = self.engine.get("dnc-c", 1.0)
-        try:
-            c_ok = not isinstance(c, bool) and float(c) > 0
-        except (TypeError, ValueError):
-            c_ok = False
-        if not c_ok:
-            raise ValueError(f"engine.dnc-c must be a number > 0 (got {c!r})")
-        it, tau = self.engine.get("cclip-iters", 3), self.engine.get("cclip-tau", "auto")
-        if isinstance(it, bool) or not isinstance(it, int) or it < 1:
-            raise ValueError(f"engine.cclip-iters must be an integer >= 1 (got {it!r})")
-        try:  # (a YAML string such as "1e-3" is a number here too)
-            tau_ok = tau == "auto" or (not isinstance(tau, bool) and float(tau) > 0)
-        except (TypeError, ValueError):
-            tau_ok = False
-        if not tau_ok:
-            raise ValueError(f"engine.cclip-tau must be 'auto' or a number > 0 (got {tau!r})")
+        for k in RULE_KNOBS:
+            k.check(self.engine.get(k.key, k.default), "engine.")
         return self
 
     def to_dict(self) -> Dict[str, Any]:

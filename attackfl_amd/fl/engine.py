@@ -38,7 +38,7 @@ from .. import ops
 from ..agg import AGGREGATORS, AggResult
 from ..agg import host_info as agg_host_info
 from ..attacks import DistanceEngine, host_info, run_attack
-from ..config import AttackSpec, Config
+from ..config import RULE_KNOBS, AttackSpec, Config
 from ..data import DeviceTable, resolve_dataset
 from ..detect import HyperDetector
 from ..eval import Validation
@@ -792,18 +792,12 @@ class FLEngine:
     # SERVER
     # ------------------------------------------------------------------------------------------
     def _rule_args(self) -> dict:
-        """The keywords every rule receives (each reads its own): the round's seed (scionfl), ``gmm-rank``, ``byz-f``
-        (multi_krum / bulyan / dnc), ``geomed-iters``, ``geomed-nu``, dnc's ``dnc-iters``, ``dnc-sub-dim``, ``dnc-c``
-        (dnc keys its column sub-samples with the round's seed) and cclip's ``centre`` (the global model the round
-        started from: in the early launch the launch's START; None before there is one), ``cclip-iters``, ``cclip-tau``."""
+        """The keywords every rule receives (each reads its own): every knob of ``config.RULE_KNOBS`` under its keyword,
+        the round's seed (scionfl; dnc keys its column sub-samples with it) and cclip's ``centre`` (the global model the
+        round started from: in the early launch the launch's START; None before there is one)."""
         e = self.cfg.engine
-        tau = e.get("cclip-tau", "auto")
-        return {"seed": self.seed * 13 + self.round_no, "gmm_rank": int(e.get("gmm-rank", 1)),
-                "byz_f": e.get("byz-f", "auto"), "geomed_iters": int(e.get("geomed-iters", 100)),
-                "geomed_nu": float(e.get("geomed-nu", 1e-6)), "dnc_iters": int(e.get("dnc-iters", 1)),
-                "dnc_sub_dim": int(e.get("dnc-sub-dim", 10000)), "dnc_c": float(e.get("dnc-c", 1.0)),
-                "centre": self.global_params, "cclip_iters": int(e.get("cclip-iters", 3)),
-                "cclip_tau": tau if tau == "auto" else float(tau)}
+        return {**{k.kw: k.check(e.get(k.key, k.default), coerce=True) for k in RULE_KNOBS},
+                "seed": self.seed * 13 + self.round_no, "centre": self.global_params}
 
     def _server_step(self, U: torch.Tensor, sizes: torch.Tensor, attackers: torch.Tensor,
                      ok_all: Optional[torch.Tensor], w: Optional[torch.Tensor] = None, gen_key=None):

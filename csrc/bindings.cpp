@@ -69,26 +69,39 @@ torch::Tensor pairwise_sqdist(torch::Tensor G) {
   return D;
 }
 
-// pairwise squared distances through the Gram matrix of the rows centred on a device-chosen row, fp64 MFMA (K <= 64)
-torch::Tensor pairwise_sqdist_gram(torch::Tensor G) {
+// M (after its check_dev): [n, n], 1 <= n <= 64, the one-wave kernels' matrix (``what``: the caller's text) -> n
+int64_t check_square64(const torch::Tensor& M, const char* what) {
+  TORCH_CHECK(M.dim() == 2 && M.size(1) == M.size(0) && M.size(0) >= 1 && M.size(0) <= 64, what);
+  return M.size(0);
+}
+
+// the scratch of a Gram pass over U [K <= 64, P]: block partials, the picked centre, the final centre's K x K Gram (tail)
+torch::Tensor gram_scratch(const torch::Tensor& U) {
+  return torch::empty({(long)afl_gram_partials((int)U.size(0), U.size(1))}, U.options().dtype(torch::kFloat64));
+}
+
+// the two-pass Gram of the rows centred on a device-chosen row, fp64 MFMA (K <= 64) -> (the pairwise squared
+// distances D [K, K], the scratch)
+std::pair<torch::Tensor, torch::Tensor> gram_two_pass(const torch::Tensor& G) {
   check_dev(G, "G", torch::kFloat32);
   TORCH_CHECK(G.dim() == 2 && G.size(0) >= 1 && G.size(0) <= 64, "G must be [K <= 64, P]");
   const int K = G.size(0);
-  const long P = G.size(1);
   auto D = torch::zeros({K, K}, G.options().dtype(torch::kFloat64));
-  auto scratch = torch::empty({(long)afl_gram_partials(K, P)}, D.options());
-  TORCH_CHECK(afl_pair_sqdist_gram(G.data_ptr<float>(), K, P, scratch.data_ptr<double>(), D.data_ptr<double>(),
+  auto scratch = gram_scratch(G);
+  TORCH_CHECK(afl_pair_sqdist_gram(G.data_ptr<float>(), K, G.size(1), scratch.data_ptr<double>(), D.data_ptr<double>(),
                                    cur()) == 0, "gram launch failed");
   AFL_CHECK_LAUNCH();
-  return D;
+  return {D, scratch};
 }
+
+torch::Tensor pairwise_sqdist_gram(torch::Tensor G) { return gram_two_pass(G).first; }
 
 // GMM filter (agg.gmm): G = centred Gram [n, n] fp64, att [n] uint8 -> (keep [n] uint8, info [3] fp64)
 std::vector<torch::Tensor> gmm_filter(torch::Tensor G, torch::Tensor att, int64_t rank) {
   check_dev(G, "G", torch::kFloat64);
   check_dev(att, "att", torch::kUInt8);
-  const int64_t n = G.size(0);
-  TORCH_CHECK(G.dim() == 2 && G.size(1) == n && att.numel() == n && n >= 1 && n <= 64, "gmm_filter: G [n, n], n <= 64");
+  const int64_t n = check_square64(G, "gmm_filter: G [n, n], n <= 64");
+  TORCH_CHECK(att.numel() == n, "gmm_filter: G [n, n], n <= 64");
   auto keep = torch::zeros({n}, att.options());
   auto info = torch::zeros({3}, G.options());
   TORCH_CHECK(afl_gmm_filter(G.data_ptr<double>(), (int)n, att.data_ptr<uint8_t>(), keep.data_ptr<uint8_t>(),
@@ -111,8 +124,7 @@ torch::Tensor fxsum_test(torch::Tensor vals, int64_t seed, int64_t mode) {
 // FLTracer PCA(1) scores (agg.fltracer): G = centred Gram [n, n] fp64 -> z [n] fp64
 torch::Tensor top_pc(torch::Tensor G, int64_t sweeps) {
   check_dev(G, "G", torch::kFloat64);
-  const int64_t n = G.size(0);
-  TORCH_CHECK(G.dim() == 2 && G.size(1) == n && n >= 1 && n <= 64, "top_pc: G [n, n], n <= 64");
+  const int64_t n = check_square64(G, "top_pc: G [n, n], n <= 64");
   auto z = torch::empty({n}, G.options());
   TORCH_CHECK(afl_top_pc(G.data_ptr<double>(), (int)n, (int)sweeps, z.data_ptr<double>(), cur()) == 0,
               "top_pc launch failed");
@@ -171,8 +183,7 @@ std::vector<torch::Tensor> dnc_run(torch::Tensor src, int64_t b, int64_t iters, 
 // uint8, first-pass scores [n] fp64)
 std::vector<torch::Tensor> krum_select(torch::Tensor D, int64_t f, int64_t rounds, bool iterated) {
   check_dev(D, "D", torch::kFloat64);
-  const int64_t n = D.size(0);
-  TORCH_CHECK(D.dim() == 2 && D.size(1) == n && n >= 1 && n <= 64, "krum_select: D [n, n], n <= 64");
+  const int64_t n = check_square64(D, "krum_select: D [n, n], n <= 64");
   TORCH_CHECK(f >= 0 && f <= n && rounds >= 1 && rounds <= n, "krum_select: n = ", n, " needs 0 <= f <= n and 1 <= ",
               "rounds <= n (got f = ", f, ", rounds = ", rounds, ")");
   auto sel = torch::zeros({rounds}, D.options().dtype(torch::kInt32));
@@ -235,9 +246,8 @@ torch::Tensor bulyan_coord(torch::Tensor U, torch::Tensor sel, int64_t beta) {
 std::vector<torch::Tensor> geomed_weights(torch::Tensor G, torch::Tensor alpha, int64_t iters, double nu) {
   check_dev(G, "G", torch::kFloat64);
   check_dev(alpha, "alpha", torch::kFloat64);
-  const int64_t n = G.size(0);
-  TORCH_CHECK(G.dim() == 2 && G.size(1) == n && alpha.numel() == n && n >= 1 && n <= 64,
-              "geomed_weights: G [n, n], alpha [n], n <= 64");
+  const int64_t n = check_square64(G, "geomed_weights: G [n, n], alpha [n], n <= 64");
+  TORCH_CHECK(alpha.numel() == n, "geomed_weights: G [n, n], alpha [n], n <= 64");
   TORCH_CHECK(iters >= 1 && iters <= INT_MAX && nu > 0.0, "geomed_weights: iters >= 1 and nu > 0 (got ", iters, ", ", nu,
               ")");
   auto w = torch::zeros({n}, G.options());
@@ -260,7 +270,7 @@ torch::Tensor gram_anchored(torch::Tensor U, torch::Tensor anchor) {
   TORCH_CHECK(anchor.dim() == 1 && anchor.size(0) == P && anchor.device() == U.device(),
               "gram_anchored: anchor [P] on U's device (got ", anchor.numel(), " values for P = ", P, ")");
   auto gram = torch::zeros({K, K}, U.options().dtype(torch::kFloat64));
-  auto scratch = torch::empty({(long)afl_gram_partials(K, P)}, gram.options());
+  auto scratch = gram_scratch(U);
   TORCH_CHECK(afl_gram_anchored(U.data_ptr<float>(), K, P, anchor.data_ptr<float>(), scratch.data_ptr<double>(),
                                 gram.data_ptr<double>(), cur()) == 0, "gram_anchored launch failed");
   AFL_CHECK_LAUNCH();
@@ -273,9 +283,8 @@ std::vector<torch::Tensor> cclip_weights(torch::Tensor G, torch::Tensor alpha, t
   check_dev(G, "G", torch::kFloat64);
   check_dev(alpha, "alpha", torch::kFloat64);
   check_dev(c0, "c0", torch::kFloat64);
-  const int64_t n = G.size(0);
-  TORCH_CHECK(G.dim() == 2 && G.size(1) == n && alpha.numel() == n && c0.numel() == n && n >= 1 && n <= 64,
-              "cclip_weights: G [n, n], alpha [n], c0 [n], n <= 64");
+  const int64_t n = check_square64(G, "cclip_weights: G [n, n], alpha [n], c0 [n], n <= 64");
+  TORCH_CHECK(alpha.numel() == n && c0.numel() == n, "cclip_weights: G [n, n], alpha [n], c0 [n], n <= 64");
   TORCH_CHECK(alpha.device() == G.device() && c0.device() == G.device(), "cclip_weights: every tensor on G's device");
   TORCH_CHECK(iters >= 1 && iters <= 65535 && tau == tau, "cclip_weights: 1 <= iters <= 65535 and tau a number (got ",
               iters, ", ", tau, ")");
@@ -310,15 +319,8 @@ torch::Tensor anchored_rows(torch::Tensor U, torch::Tensor c, torch::Tensor anch
 // fp64-MFMA pass (H: the Gram of the rows centred on the pass's final centre row, the scratch tail) followed by the
 // double centring C = H - rowmean - colmean + mean, which does not depend on the centre beyond rounding
 std::vector<torch::Tensor> gram_centred(torch::Tensor G) {
-  check_dev(G, "G", torch::kFloat32);
-  TORCH_CHECK(G.dim() == 2 && G.size(0) >= 1 && G.size(0) <= 64, "G must be [K <= 64, P]");
-  const int K = G.size(0);
-  const long P = G.size(1);
-  auto D = torch::zeros({K, K}, G.options().dtype(torch::kFloat64));
-  auto scratch = torch::empty({(long)afl_gram_partials(K, P)}, D.options());
-  TORCH_CHECK(afl_pair_sqdist_gram(G.data_ptr<float>(), K, P, scratch.data_ptr<double>(), D.data_ptr<double>(),
-                                   cur()) == 0, "gram launch failed");
-  AFL_CHECK_LAUNCH();
+  auto [D, scratch] = gram_two_pass(G);
+  const long K = D.size(0);
   auto H = scratch.narrow(0, scratch.numel() - (long)K * K, (long)K * K).view({K, K});
   auto C = H - H.mean(0, true) - H.mean(1, true) + H.mean();
   return {C, D};

@@ -18,12 +18,21 @@
 //   anchored_rows   out = g + sum_i c_i (U_i - g) (fp64 weights, fp64 accumulate): centred clipping's row pass
 //   dnc_gram        DnC: fp64-MFMA Grams over keyed random column subsets, all iterations in one launch
 //   dnc_select      DnC: top eigenpair, scores, ranked drop, mask intersection and weights, one wave
+// Shared: gram_for_tiles (the host's one T = 1 .. 4 launch of gram_f64 and dnc_gram) and lds_load_square (the matrix load
+// of geomed_weights and cclip_weights).  The device code of the two Gram kernels and of the one-wave kernels is otherwise
+// kept per kernel: folding it cost 0.2 - 3 % in single-call timings (profiles/ab_agg_refactor.md).
 //
 // Every reduction is two-pass with a fixed summation order (no float atomics), so results are
 // bit-identical across ranks: the replicated server state on each rank stays in lock-step.
 #include "common.h"
 #include "kernels.h"
 #include "plan_perm.h"
+#include <type_traits>
+
+// A [n][ld] in LDS <- the n x n fp64 matrix G (the one-wave n <= 64 kernels: 64-thread blocks)
+__device__ __forceinline__ void lds_load_square(double* __restrict__ A, int ld, const double* __restrict__ G, int n) {
+  for (int e = threadIdx.x; e < n * n; e += 64) A[e / n * ld + e % n] = G[e];
+}
 
 // ============================================================================ colstats
 __global__ void __launch_bounds__(256) k_colstats(const float* __restrict__ G, int K, long P, float* __restrict__ mean,
@@ -325,26 +334,33 @@ int afl_gram_partials(int K, long P) {
   return afl_cdiv(P, GR_CH) * T * (T + 1) / 2 * 256 + 1 + K * K;
 }
 
-static void gram_pass(const float* G, int K, long P, int T, int nb, const int* centre, double* partial, double* gram,
-                      double* D, int* pick, hipStream_t s, const float* anchor = nullptr) {
-  switch (T) {
-    case 1: hipLaunchKernelGGL(k_gram_f64<1>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial, anchor); break;
-    case 2: hipLaunchKernelGGL(k_gram_f64<2>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial, anchor); break;
-    case 3: hipLaunchKernelGGL(k_gram_f64<3>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial, anchor); break;
-    default: hipLaunchKernelGGL(k_gram_f64<4>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial, anchor); break;
+// launch(std::integral_constant<int, T>) for the K <= GR_MAXK rows' tile count T: where a Gram kernel's variant is chosen
+template <class Launch>
+static void gram_for_tiles(int K, Launch&& launch) {
+  switch ((K + 15) / 16) {
+    case 1: launch(std::integral_constant<int, 1>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    case 3: launch(std::integral_constant<int, 3>{}); break;
+    default: launch(std::integral_constant<int, 4>{}); break;
   }
-  hipLaunchKernelGGL(k_gram_reduce, dim3(1), dim3(256), 0, s, partial, nb, K, T, centre, gram, D, pick);
+}
+
+static void gram_pass(const float* G, int K, long P, const int* centre, double* partial, double* gram, double* D,
+                      int* pick, hipStream_t s, const float* anchor = nullptr) {
+  const int nb = afl_cdiv(P, GR_CH);
+  gram_for_tiles(K, [&](auto t) {
+    hipLaunchKernelGGL(k_gram_f64<decltype(t)::value>, dim3(nb), dim3(256), 0, s, G, K, P, centre, partial, anchor);
+  });
+  hipLaunchKernelGGL(k_gram_reduce, dim3(1), dim3(256), 0, s, partial, nb, K, (K + 15) / 16, centre, gram, D, pick);
 }
 
 int afl_pair_sqdist_gram(const float* G, int K, long P, double* partial, double* D, hipStream_t s) {
   if (K < 1 || K > GR_MAXK || P < 1) return (int)hipErrorInvalidValue;
-  const int T = (K + 15) / 16, nb = afl_cdiv(P, GR_CH);
-  const long np = (long)nb * T * (T + 1) / 2 * 256;
-  int* centre = (int*)(partial + np);
-  double* gram = partial + np + 1;
+  double* gram = partial + afl_gram_partials(K, P) - K * K;  // (the scratch: partials, the centre word, the Gram)
+  int* centre = (int*)(gram - 1);
   // (K <= 2: every row is as central as row 0, one pass)
-  gram_pass(G, K, P, T, nb, nullptr, partial, gram, D, K > 2 ? centre : nullptr, s);
-  if (K > 2) gram_pass(G, K, P, T, nb, centre, partial, gram, D, nullptr, s);
+  gram_pass(G, K, P, nullptr, partial, gram, D, K > 2 ? centre : nullptr, s);
+  if (K > 2) gram_pass(G, K, P, centre, partial, gram, D, nullptr, s);
   return (int)hipGetLastError();
 }
 
@@ -353,8 +369,7 @@ int afl_pair_sqdist_gram(const float* G, int K, long P, double* partial, double*
 int afl_gram_anchored(const float* U, int K, long P, const float* anchor, double* partial, double* gram,
                       hipStream_t s) {
   if (K < 1 || K > GR_MAXK || P < 1 || anchor == nullptr) return (int)hipErrorInvalidValue;
-  const int T = (K + 15) / 16, nb = afl_cdiv(P, GR_CH);
-  gram_pass(U, K, P, T, nb, nullptr, partial, gram, nullptr, nullptr, s, anchor);
+  gram_pass(U, K, P, nullptr, partial, gram, nullptr, nullptr, s, anchor);
   return (int)hipGetLastError();
 }
 
@@ -1127,12 +1142,9 @@ int afl_dnc_gram(const float* U, int K, long P, long b, int iters, uint64_t seed
   const long nv = b < P ? b : P;
   const int natural = b >= P ? 1 : 0;
   const dim3 grid((unsigned)afl_cdiv(nv, GR_CH), (unsigned)iters);
-  switch ((K + 15) / 16) {
-    case 1: hipLaunchKernelGGL(k_dnc_gram<1>, grid, dim3(256), 0, s, U, K, P, nv, natural, seed, partial); break;
-    case 2: hipLaunchKernelGGL(k_dnc_gram<2>, grid, dim3(256), 0, s, U, K, P, nv, natural, seed, partial); break;
-    case 3: hipLaunchKernelGGL(k_dnc_gram<3>, grid, dim3(256), 0, s, U, K, P, nv, natural, seed, partial); break;
-    default: hipLaunchKernelGGL(k_dnc_gram<4>, grid, dim3(256), 0, s, U, K, P, nv, natural, seed, partial); break;
-  }
+  gram_for_tiles(K, [&](auto t) {
+    hipLaunchKernelGGL(k_dnc_gram<decltype(t)::value>, grid, dim3(256), 0, s, U, K, P, nv, natural, seed, partial);
+  });
   return (int)hipGetLastError();
 }
 
@@ -1496,10 +1508,7 @@ __global__ void __launch_bounds__(64) k_geomed_weights(const double* __restrict_
                                                        double* __restrict__ info) {
   __shared__ double A[GMM_MAXN * KS_LD], wb[GMM_MAXN];
   const int i = threadIdx.x;
-  for (int e = i; e < n * n; e += 64) {
-    const int r = e / n, c = e - r * n;
-    A[r * KS_LD + c] = G[e];
-  }
+  lds_load_square(A, KS_LD, G, n);
   const double al = i < n ? alpha[i] : 0.0;
   double wi = al, prev = INFINITY, obj = 0.0;
   int it = 0;
@@ -1553,10 +1562,7 @@ __global__ void __launch_bounds__(64) k_cclip_weights(const double* __restrict__
                                                       double* __restrict__ c, double* __restrict__ info) {
   __shared__ double A[GMM_MAXN * KS_LD], cb[GMM_MAXN], db[GMM_MAXN], tau_s;
   const int i = threadIdx.x;
-  for (int e = i; e < n * n; e += 64) {
-    const int r = e / n, cc = e - r * n;
-    A[r * KS_LD + cc] = G[e];
-  }
+  lds_load_square(A, KS_LD, G, n);
   __syncthreads();
   const double gii = i < n ? A[i * KS_LD + i] : 0.0;
   const bool fin = i < n && gram_finite(gii);
