@@ -44,7 +44,6 @@ namespace t2 {
 using namespace oc;
 
 
-
 // ----------------------------------------------------------------------------------- LDS maps (bytes)
 // branch workgroup
 // dense image compact (k unpermuted: the K <= 16 MFMA reads k = 4g .. 4g + 3 at byte 8g), which pays for 32-byte
@@ -207,6 +206,50 @@ enum { ABL_U3 = 1, ABL_UADAM = 2, ABL_UDW = 4, ABL_COLSUM = 8, ABL_HEADUPD = 16,
 
 
 
+// The granule hand-off of onchip.h (gr_put / gr_get) with the slot's wave-uniform part of the address in the buffer
+// instruction's SCALAR offset: the per-lane part, 16 * lane + 1024 k, is the same four VGPRs for every slot, where
+// the all-VGPR form kept one hoisted address per granule store / load live across the whole step (4 + 4 per branch
+// wave) — the values the 256-register allocation spilled first.  (The head keeps onchip.h's form: there the extra
+// SGPRs cost a second spill VGPR and sent a weight to scratch; profiles/ab_tf2_frag_pipeline.log.)
+__device__ __forceinline__ int gr_soff(int dir, int src, int wave) { return dir * GR_DIR_BYTES + (src * 8 + wave) * 4096; }
+__device__ __forceinline__ void gr_put_s(__amdgpu_buffer_rsrc_t rg, int soff, int lane16, const u32x4 (&u)[2],
+                                         uint32_t tag) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int j = 2 * (k & 1);
+    __builtin_amdgcn_raw_buffer_store_b128(u32x4{u[k >> 1][j], tag, u[k >> 1][j + 1], tag}, rg, lane16 + k * 1024, soff, 16);
+    store_guard();
+  }
+}
+template <int S>
+__device__ __forceinline__ uint32_t gr_get_s(__amdgpu_buffer_rsrc_t rg, const int (&soff)[S], int lane16,
+                                             u32x4 (&out)[2 * S], uint32_t want, int shift, gu32* tmo, int lane) {
+  for (long spins = 0;; ++spins) {
+    u32x4 v[4 * S];
+#pragma unroll
+    for (int s = 0; s < S; ++s)
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        v[4 * s + k] = __builtin_amdgcn_raw_buffer_load_b128(rg, lane16 + k * 1024, soff[s], 16);
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 4 * S; ++i) ok = ok && (v[i][1] >> shift) == want && (v[i][3] >> shift) == want;
+    if (__builtin_amdgcn_ballot_w64(!ok) == 0) {
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        out[2 * s] = u32x4{v[4 * s][0], v[4 * s][2], v[4 * s + 1][0], v[4 * s + 1][2]};
+        out[2 * s + 1] = u32x4{v[4 * s + 2][0], v[4 * s + 2][2], v[4 * s + 3][0], v[4 * s + 3][2]};
+      }
+      return __builtin_amdgcn_readfirstlane(v[0][1]);
+    }
+    if (spins > fk::XWG_MAX_SPINS) {
+      if (lane == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return 0xFFFFFFFFu;
+    }
+    __builtin_amdgcn_s_sleep(1);
+  }
+}
+
 // Wave priorities: the two waves sharing a SIMD (w and w + 4) run the same critical chain, and the
 // arbiter favours the older one, so waves 4-7 finished the forward 1.35 us after waves 0-3 (per-wave
 // stamps) while waves 0-3 already hashed the NEXT step's dropout masks beside them.  Critical sections
@@ -269,9 +312,9 @@ __device__ __forceinline__ void load16(float (&x)[16], const uint32_t (&d)[8]) {
 // in the workspace units, see br_update):
 //  * cmp: NCMP "compact" entries, the bias / LayerNorm vectors (VEC index e < 648).  An entry belongs to the thread
 //    whose registers hold its gradient sum at the end of br_update's units (vec_entry), so the vector Adam needs
-//    no staging and no barrier: at most two entries per thread, one pass of vec_adam<2> per wave.  (The dense,
-//    ffn.0 and ffn.3 weights were compact entries too; since round 6 the leaders update them as tiles — br_update,
-//    small units.)
+//    no staging and no barrier: at most two entries per thread, riding in the stages of a unit's Adam (br_update).
+//    (The dense, ffn.0 and ffn.3 weights were compact entries too; since round 6 the leaders update them as tiles —
+//    br_update, small units.)
 constexpr int NCMP = 2;
 struct BrState {
   VS cmp[NCMP];
@@ -319,6 +362,22 @@ __device__ __forceinline__ void br_masks(uint32_t key, int r, int g, uint32_t& m
   mk1 = matt | (kf << 4);
 }
 
+// Fragment pipeline (br_forward, br_backward).  Each sub-phase consumes bf16 weight-image fragments that depend on no
+// activation, but the sched_barrier in front of it keeps their ds_reads behind the previous sub-phase's epilogue VALU,
+// so every layer boundary exposed one LDS round trip on a latency-bound chain.  The k-step-0 fragments of the NEXT
+// sub-phase's first MFMAs (both k-steps where they are small) are therefore issued at the top of the CURRENT one,
+// above a fence of their own — in flight under its MFMAs and epilogue — and pinned at its end like bp.f3 (br_bwd_pre),
+// so they are neither sunk nor re-read.  The MFMA order is unchanged: results are bit-identical by construction.
+// Safe because the forward's images are final between the step's end barrier and this step's update, and in the
+// backward a wave reads an image only BEFORE it signals the counter that frees it (ffn.0 / out_proj: A, in_proj.v:
+// B): a prefetch inside the same wave's backward is issued even earlier than the read it replaces, and lds_signal
+// drains the wave's LDS reads before the count moves.
+template <int N, class V>
+__device__ __forceinline__ void pin(V (&f)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) asm volatile("" : "+v"(f[i]));
+}
+
 template <int BR>
 __device__ __forceinline__ void br_forward(uchar* smem, const float (&xin)[4], uint32_t mk0, uint32_t mk1, Saved& sv,
                                            u32x4 (&outp)[2], int lane, int wave) {
@@ -329,13 +388,23 @@ __device__ __forceinline__ void br_forward(uchar* smem, const float (&xin)[4], u
   st4<TK16>(smem + B_XIN, r, g, xin);
   // ---- dense (K = din <= 16 padded to 32) + GELU
   float h0[16];
+  s8v pfv[4], pfo[4], pf1[2];  // k-step-0 fragments of v / out_proj, both of ffn.0: loaded one sub-phase ahead
+  s4v pf3[4];                  // ffn.3's
   sb();
   {
     const s4v bx = bfrag4(xin);
     f4v acc[4];
+    s4v wd[4];
 #pragma unroll
     for (int T = 0; T < 4; ++T)
-      acc[T] = mma16(*(const LDS_AS s4v*)(smem + B_IMG_D + (16 * T + (lane & 15)) * LDDN + 8 * (lane >> 4)), bx, Z4);
+      wd[T] = *(const LDS_AS s4v*)(smem + B_IMG_D + (16 * T + (lane & 15)) * LDDN + 8 * (lane >> 4));
+    // (the dense fragments first, the v fragments behind them: LDS returns in order)
+    sb();
+#pragma unroll
+    for (int T = 0; T < 4; ++T) pfv[T] = wfrag(smem + B_IMG_V, LDVO, T, 0, lane);
+    sb();
+#pragma unroll
+    for (int T = 0; T < 4; ++T) acc[T] = mma16(wd[T], bx, Z4);
     float bd[16], gp[16];
     vec16g(bd, vg + VS_DB * 256);
 #pragma unroll
@@ -352,17 +421,24 @@ __device__ __forceinline__ void br_forward(uchar* smem, const float (&xin)[4], u
     save16(sv.gp, gp);
 #pragma unroll
     for (int t = 0; t < 4; ++t) st4<TK64>(smem + B_H0, r, 4 * t + g, h0 + 4 * t);
+    pin(pfv);
   }
   // ---- v projection, attention dropout per (row, head); at L = 1 softmax == 1, so attn = drop(v)
   float a[16];
   sb();
   {
+    s8v w1[4];
+#pragma unroll
+    for (int T = 0; T < 4; ++T) w1[T] = wfrag(smem + B_IMG_V, LDVO, T, 1, lane);
+#pragma unroll
+    for (int T = 0; T < 4; ++T) pfo[T] = wfrag(smem + B_IMG_O, LDVO, T, 0, lane);
+    sb();
     const s8v b0 = bfrag(h0, 0), b1 = bfrag(h0, 1);
     f4v acc[4];
 #pragma unroll
     for (int T = 0; T < 4; ++T) {
-      acc[T] = mma(wfrag(smem + B_IMG_V, LDVO, T, 0, lane), b0, Z4);
-      acc[T] = mma(wfrag(smem + B_IMG_V, LDVO, T, 1, lane), b1, acc[T]);
+      acc[T] = mma(pfv[T], b0, Z4);
+      acc[T] = mma(w1[T], b1, acc[T]);
     }
     sv.matt = mk1 & 0xFu;
     float bv[16];
@@ -375,17 +451,24 @@ __device__ __forceinline__ void br_forward(uchar* smem, const float (&xin)[4], u
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) st4<TK64>(smem + B_A, r, 4 * t + g, a + 4 * t);
+    pin(pfo);
   }
   // ---- out projection, dropout, residual, LayerNorm 1
   float x1n[16];
   sb();
   {
+    s8v w1[4];
+#pragma unroll
+    for (int T = 0; T < 4; ++T) w1[T] = wfrag(smem + B_IMG_O, LDVO, T, 1, lane);
+    pf1[0] = wfrag(smem + B_IMG_F1, LD64, 0, 0, lane);
+    pf1[1] = wfrag(smem + B_IMG_F1, LD64, 0, 1, lane);
+    sb();
     const s8v b0 = bfrag(a, 0), b1 = bfrag(a, 1);
     f4v acc[4];
 #pragma unroll
     for (int T = 0; T < 4; ++T) {
-      acc[T] = mma(wfrag(smem + B_IMG_O, LDVO, T, 0, lane), b0, Z4);
-      acc[T] = mma(wfrag(smem + B_IMG_O, LDVO, T, 1, lane), b1, acc[T]);
+      acc[T] = mma(pfo[T], b0, Z4);
+      acc[T] = mma(w1[T], b1, acc[T]);
     }
     sv.m1 = mk0 & 0xFFFFu;
     float bo[16];
@@ -406,13 +489,17 @@ __device__ __forceinline__ void br_forward(uchar* smem, const float (&xin)[4], u
     affine2(x1n, x1, gm, bt);
 #pragma unroll
     for (int t = 0; t < 4; ++t) st4<TK64>(smem + B_X1N, r, 4 * t + g, x1n + 4 * t);
+    pin(pf1);
   }
   // ---- ffn.0 (64 -> 6, one output tile) + GELU + dropout
   float f2v[4];
   sb();
   {
-    f4v acc = mma(wfrag(smem + B_IMG_F1, LD64, 0, 0, lane), bfrag(x1n, 0), Z4);
-    acc = mma(wfrag(smem + B_IMG_F1, LD64, 0, 1, lane), bfrag(x1n, 1), acc);
+#pragma unroll
+    for (int T = 0; T < 4; ++T) pf3[T] = wfrag4(smem + B_IMG_F2, LD32, T, lane);
+    sb();
+    f4v acc = mma(pf1[0], bfrag(x1n, 0), Z4);
+    acc = mma(pf1[1], bfrag(x1n, 1), acc);
     const f4v bf = g < 2 ? *(const LDS_AS f4v*)(vg + VS_F1B * 4) : Z4;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -422,6 +509,7 @@ __device__ __forceinline__ void br_forward(uchar* smem, const float (&xin)[4], u
       sv.gk[i] = keepf(gp * INV_K01, mk1, 4 + i);
     }
     st4<TK16>(smem + B_F2, r, g, f2v);
+    pin(pf3);
   }
   // ---- ffn.3 (6 -> 64, K padded to 32), dropout, residual, LayerNorm 2, LayerNorm 3 (x_bn)
   sb();
@@ -429,7 +517,7 @@ __device__ __forceinline__ void br_forward(uchar* smem, const float (&xin)[4], u
     const s4v bf = bfrag4(f2v);
     f4v acc[4];
 #pragma unroll
-    for (int T = 0; T < 4; ++T) acc[T] = mma16(wfrag4(smem + B_IMG_F2, LD32, T, lane), bf, Z4);
+    for (int T = 0; T < 4; ++T) acc[T] = mma16(pf3[T], bf, Z4);
     sv.m2 = mk0 >> 16;
     float b3[16];
     vec16g(b3, vg + VS_F2B * 256);
@@ -511,8 +599,13 @@ __device__ __forceinline__ void br_backward(uchar* smem, const float (&dout)[16]
     ln_bwd2(dr2, dx, xh, sv.rstd2, gm);
   }
   float df0[4];
+  s4v pt1[4];          // the transposed ffn.0 fragments, loaded one sub-phase ahead (fragment pipeline, above)
+  s8v pto[4], ptv[4];  // the k-step-0 transposed out_proj / in_proj.v fragments
   sb();
   {  // d(ffn.3 out) -> ffn.3 backward (d f2) -> d(ffn.0 pre-activation)
+#pragma unroll
+    for (int T = 0; T < 4; ++T) pt1[T] = wtfrag4(smem + B_IMG_F1, LD64, T, lane);
+    sb();
     float d3[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) d3[j] = keepf(dr2[j] * INV_K01, sv.m2, j);
@@ -523,16 +616,20 @@ __device__ __forceinline__ void br_backward(uchar* smem, const float (&dout)[16]
 #pragma unroll
     for (int i = 0; i < 4; ++i) df0[i] = acc[i] * sv.gk[i];
     st4<TK16>(smem + B_DF0, r, g, df0);
+    pin(pt1);
   }
   lds_signal(smem, B_CNT_C, lane);  // DF3 / DF0 rows stored: the ffn weight tiles may be computed
   float dr1[16];
   sb();
   {  // ffn.0 backward (d x1n) + residual, LayerNorm 1 backward
+#pragma unroll
+    for (int T = 0; T < 4; ++T) pto[T] = wtfrag<true>(smem + B_IMG_O, LDVO, T, 0, lane);
+    sb();
     const s4v bd = bfrag4(df0);
     float dx[16];
 #pragma unroll
     for (int T = 0; T < 4; ++T) {
-      const f4v acc = mma16(wtfrag4(smem + B_IMG_F1, LD64, T, lane), bd, Z4);
+      const f4v acc = mma16(pt1[T], bd, Z4);
 #pragma unroll
       for (int i = 0; i < 4; ++i) dx[4 * T + i] = acc[i] + dr2[4 * T + i];
     }
@@ -544,10 +641,14 @@ __device__ __forceinline__ void br_backward(uchar* smem, const float (&dout)[16]
     if (!ABL(K, ABL_COLSUM)) ln_colsum(smem, 1, dx, lane);
     vec16g(gm, vg + VS_G1 * 256);
     ln_bwd2(dr1, dx, xh, sv.rstd1, gm);
+    pin(pto);
   }
   float dv[16];
   sb();
   {  // out_proj backward: d a = d o . Wo ; d v = attention-dropout'(d a)
+#pragma unroll
+    for (int T = 0; T < 4; ++T) ptv[T] = wtfrag<true>(smem + B_IMG_V, LDVO, T, 0, lane);
+    sb();
     float dO[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) dO[j] = keepf(dr1[j] * INV_K01, sv.m1, j);
@@ -556,7 +657,7 @@ __device__ __forceinline__ void br_backward(uchar* smem, const float (&dout)[16]
     const s8v b0 = bfrag(dO, 0), b1 = bfrag(dO, 1);
 #pragma unroll
     for (int T = 0; T < 4; ++T) {
-      f4v acc = mma(wtfrag<true>(smem + B_IMG_O, LDVO, T, 0, lane), b0, Z4);
+      f4v acc = mma(pto[T], b0, Z4);
       acc = mma(wtfrag<true>(smem + B_IMG_O, LDVO, T, 1, lane), b1, acc);
       const float m = keepf(INV_K01, sv.matt, T);
 #pragma unroll
@@ -564,6 +665,7 @@ __device__ __forceinline__ void br_backward(uchar* smem, const float (&dout)[16]
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) st4<TK64>(smem + B_DV, r, 4 * t + g, dv + 4 * t);
+    pin(ptv);
   }
   lds_signal(smem, B_CNT_A, lane);  // DO / DV rows stored, out_proj image read: its block may be updated
   sb();
@@ -573,7 +675,7 @@ __device__ __forceinline__ void br_backward(uchar* smem, const float (&dout)[16]
     load16(gp, sv.gp);
 #pragma unroll
     for (int T = 0; T < 4; ++T) {
-      f4v acc = mma(wtfrag<true>(smem + B_IMG_V, LDVO, T, 0, lane), b0, Z4);
+      f4v acc = mma(ptv[T], b0, Z4);
       acc = mma(wtfrag<true>(smem + B_IMG_V, LDVO, T, 1, lane), b1, acc);
 #pragma unroll
       for (int i = 0; i < 4; ++i) dz[4 * T + i] = (acc[i] + dr1[4 * T + i]) * gp[4 * T + i];
@@ -604,10 +706,60 @@ __device__ __forceinline__ void unit_st(__amdgpu_buffer_rsrc_t rm, int ui, int j
                                          0, 0);
   store_guard();
 }
-// Adam on the 16 elements of a unit (p, m, v in U, gradients acc[a][b] of tile 2a + b), in explicit stages so the
-// 16 independent sqrt -> rcp -> fma chains overlap
-__device__ __forceinline__ void unit_adam(f4v (&U)[12], const f4v (&acc)[2][2], const AdamK& K) {
-  float p[16], mm[16], vv[16], g[16], den[16];
+// A thread's vector entries (vec_entry) on their way through a unit's Adam stages: weights (VS registers), moments,
+// gradient sums in; new weights out in pn
+struct VecAd {
+  float m[NCMP], v[NCMP], g[NCMP], pn[NCMP];
+};
+// Adam on N independent elements in explicit stages (every m / v update, every square root, every reciprocal, every
+// weight), so the N sqrt -> rcp -> fma chains overlap, with every contraction written out.  Which products of
+// `b2 v + (1 - b2) g g` and `g - keep m` the compiler fuses depends on the code around the call (it moved once:
+// profiles/ab_tf2_tail.log), and a trained model must not change with that, so each group of elements has the form
+// it compiled to before the forms were pinned (read from the ISA of the commit before, both branch instantiations):
+//   elements [0, NA)       m' = fma(c1, fma(-keep, m, g), keep m);  v' = fma(b2, v, g ((1 - b2) g))
+//   elements [NA, N - NV)  the same m';                             v' = fma(g, (1 - b2) g, b2 v)
+//   elements [N - NV, N)   m' = fma(c1, g - keep m, keep m);        v' = fma(g, (1 - b2) g, b2 v)
+//   all                    p' = fma(-(lr_bc1 m'), 1 / fma(rsqrt_bc2, sqrt(v'), eps), p)
+// unit_adam is (16, 16, 0), smu_adam (12, 4, 0): its dense tile has the first form, its ffn.3 / ffn.0 tiles the
+// second; the last NV elements are a thread's vector entries, in the form their own pass (vec_adam, until it was
+// folded in here) had pinned for them.
+template <int N, int NA, int NV>
+__device__ __forceinline__ void adam_pinned(float (&p)[N], float (&mm)[N], float (&vv)[N], const float (&g)[N],
+                                            const AdamK& K) {
+#pragma clang fp contract(off)
+  float den[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    const float mk = mm[e] * K.keep;
+    const float d = e < N - NV ? __builtin_fmaf(-K.keep, mm[e], g[e]) : g[e] - mk;
+    mm[e] = __builtin_fmaf(K.c1, d, mk);
+    const float t = (1.f - fk::B2) * g[e];
+    if (e < NA) {
+      const float t2 = g[e] * t;
+      vv[e] = __builtin_fmaf(fk::B2, vv[e], t2);
+    } else {
+      const float u = fk::B2 * vv[e];
+      vv[e] = __builtin_fmaf(g[e], t, u);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < N; ++e) den[e] = __builtin_amdgcn_sqrtf(vv[e]);
+#pragma unroll
+  for (int e = 0; e < N; ++e) den[e] = __builtin_amdgcn_rcpf(__builtin_fmaf(K.rsqrt_bc2, den[e], K.eps));
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    const float lm = K.lr_bc1 * mm[e];
+    p[e] = __builtin_fmaf(-lm, den[e], p[e]);
+  }
+}
+// Adam on the 16 elements of a unit (p, m, v in U, gradients acc[a][b] of tile 2a + b) and, when NV > 0, on the
+// thread's NV vector entries in the same stages: two more independent chains there instead of a dependent
+// sqrt -> rcp -> fma chain of their own at the end of the step
+template <int NV>
+__device__ __forceinline__ void unit_adam(f4v (&U)[12], const f4v (&acc)[2][2], const AdamK& K, VS (&pa)[NCMP],
+                                          VecAd& x) {
+  static_assert(NV == 0 || NV == NCMP, "all of the thread's vector entries or none");
+  float p[16 + NV], mm[16 + NV], vv[16 + NV], g[16 + NV];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -618,17 +770,13 @@ __device__ __forceinline__ void unit_adam(f4v (&U)[12], const f4v (&acc)[2][2], 
       g[4 * t + i] = acc[t >> 1][t & 1][i];
     }
 #pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const float mk = mm[e] * K.keep;
-    mm[e] = mk + K.c1 * (g[e] - mk);
-    vv[e] = fk::B2 * vv[e] + (1.f - fk::B2) * g[e] * g[e];
+  for (int h = 0; h < NV; ++h) {
+    mm[16 + h] = x.m[h];
+    vv[16 + h] = x.v[h];
+    p[16 + h] = ar(pa[h].p);
+    g[16 + h] = x.g[h];
   }
-#pragma unroll
-  for (int e = 0; e < 16; ++e) den[e] = __builtin_amdgcn_sqrtf(vv[e]);
-#pragma unroll
-  for (int e = 0; e < 16; ++e) den[e] = __builtin_amdgcn_rcpf(den[e] * K.rsqrt_bc2 + K.eps);
-#pragma unroll
-  for (int e = 0; e < 16; ++e) p[e] -= K.lr_bc1 * mm[e] * den[e];
+  adam_pinned<16 + NV, 16, NV>(p, mm, vv, g, K);
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -637,6 +785,13 @@ __device__ __forceinline__ void unit_adam(f4v (&U)[12], const f4v (&acc)[2][2], 
       U[4 + t][i] = vv[4 * t + i];
       U[8 + t][i] = p[4 * t + i];
     }
+#pragma unroll
+  for (int h = 0; h < NV; ++h) {
+    x.m[h] = mm[16 + h];
+    x.v[h] = vv[16 + h];
+    x.pn[h] = p[16 + h];
+    pa[h].p = aw(p[16 + h]);
+  }
 }
 // the unit's new bf16 weights into its image (rows n = 16 (Tb + b) + i16, permuted k chunk of tile Ta + a)
 __device__ __forceinline__ void unit_img(uchar* smem, const Mat& M, int Ta, int Tb, int lane, const u32x2v (&w)[4]) {
@@ -710,9 +865,12 @@ __device__ __forceinline__ void smu_elem(int s, int w4, int lane, int i, int& pi
     img = B_IMG_F1 + n * LD64 + pcol(k) * 2;
   }
 }
-// Adam on the 12 elements of a small unit (S = {m0 m1 m2, v0 v1 v2, p0 p1 p2}), gradients g[3]; new bf16 images
-__device__ __forceinline__ void smu_adam(f4v (&S)[9], const f4v (&gs)[3], const AdamK& K) {
-  float p[12], mm[12], vv[12], g[12], den[12];
+// Adam on the 12 elements of a small unit (S = {m0 m1 m2, v0 v1 v2, p0 p1 p2}), gradients g[3], and on the thread's NV
+// vector entries in the same stages (unit_adam)
+template <int NV>
+__device__ __forceinline__ void smu_adam(f4v (&S)[9], const f4v (&gs)[3], const AdamK& K, VS (&pa)[NCMP], VecAd& x) {
+  static_assert(NV == 0 || NV == NCMP, "all of the thread's vector entries or none");
+  float p[12 + NV], mm[12 + NV], vv[12 + NV], g[12 + NV];
 #pragma unroll
   for (int s = 0; s < 3; ++s)
 #pragma unroll
@@ -723,17 +881,13 @@ __device__ __forceinline__ void smu_adam(f4v (&S)[9], const f4v (&gs)[3], const 
       g[4 * s + i] = gs[s][i];
     }
 #pragma unroll
-  for (int e = 0; e < 12; ++e) {
-    const float mk = mm[e] * K.keep;
-    mm[e] = mk + K.c1 * (g[e] - mk);
-    vv[e] = fk::B2 * vv[e] + (1.f - fk::B2) * g[e] * g[e];
+  for (int h = 0; h < NV; ++h) {
+    mm[12 + h] = x.m[h];
+    vv[12 + h] = x.v[h];
+    p[12 + h] = ar(pa[h].p);
+    g[12 + h] = x.g[h];
   }
-#pragma unroll
-  for (int e = 0; e < 12; ++e) den[e] = __builtin_amdgcn_sqrtf(vv[e]);
-#pragma unroll
-  for (int e = 0; e < 12; ++e) den[e] = __builtin_amdgcn_rcpf(den[e] * K.rsqrt_bc2 + K.eps);
-#pragma unroll
-  for (int e = 0; e < 12; ++e) p[e] -= K.lr_bc1 * mm[e] * den[e];
+  adam_pinned<12 + NV, 4, NV>(p, mm, vv, g, K);
 #pragma unroll
   for (int s = 0; s < 3; ++s)
 #pragma unroll
@@ -742,6 +896,13 @@ __device__ __forceinline__ void smu_adam(f4v (&S)[9], const f4v (&gs)[3], const 
       S[3 + s][i] = vv[4 * s + i];
       S[6 + s][i] = p[4 * s + i];
     }
+#pragma unroll
+  for (int h = 0; h < NV; ++h) {
+    x.m[h] = mm[12 + h];
+    x.v[h] = vv[12 + h];
+    x.pn[h] = p[12 + h];
+    pa[h].p = aw(p[12 + h]);
+  }
 }
 // the small unit's new weights into the three images (4 consecutive (permuted) k per lane: one 8-byte store each)
 template <int BR>
@@ -751,37 +912,6 @@ __device__ __forceinline__ void smu_img(uchar* smem, const f4v (&S)[9], int w4, 
     int pi, img;
     smu_elem<BR>(s, w4, lane, 0, pi, img);
     *(LDS_AS u32x2v*)(smem + img) = u32x2v{pk2(S[6 + s][0], S[6 + s][1]), pk2(S[6 + s][2], S[6 + s][3])};
-  }
-}
-
-// Adam on a thread's vector entries in the stages of adam_staged (onchip.h), with every contraction written out:
-//   m' = fma(c1, g - keep m, keep m);  v' = fma(g, (1 - b2) g, b2 v);
-//   p' = fma(-(lr_bc1 m'), 1 / fma(rsqrt_bc2, sqrt(v'), eps), p).
-// Which products of `b2 v + (1 - b2) g g` the compiler fuses depends on the code around the call (the gradient as a
-// register select instead of an LDS read moved the fused product and the low bit of v'); a trained model must not
-// change with that, so this pass pins the form it has always compiled to.
-template <int N>
-__device__ __forceinline__ void vec_adam(VS (&pa)[N], float (&m)[N], float (&v)[N], const float (&g)[N], float (&pn)[N],
-                                         const AdamK& K) {
-#pragma clang fp contract(off)
-  float den[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    pn[i] = ar(pa[i].p);
-    const float mk = m[i] * K.keep;
-    m[i] = __builtin_fmaf(K.c1, g[i] - mk, mk);
-    const float t = (1.f - fk::B2) * g[i], u = fk::B2 * v[i];
-    v[i] = __builtin_fmaf(g[i], t, u);
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) den[i] = __builtin_amdgcn_sqrtf(v[i]);
-#pragma unroll
-  for (int i = 0; i < N; ++i) den[i] = __builtin_amdgcn_rcpf(__builtin_fmaf(K.rsqrt_bc2, den[i], K.eps));
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const float lm = K.lr_bc1 * m[i];
-    pn[i] = __builtin_fmaf(-lm, den[i], pn[i]);
-    pa[i].p = aw(pn[i]);
   }
 }
 
@@ -799,8 +929,9 @@ __device__ __forceinline__ void vec_adam(VS (&pa)[N], float (&m)[N], float (&v)[
 //   laggards  counter A (the v unit's dY rows): their in_proj.v unit, whose new bf16 weights wait for counter B (the
 //             v image is read until the end of every wave's backward).
 // The leaders then run Adam on their small unit (the dense / ffn.3 / ffn.0 tiles, workspace-resident like the
-// blocks) and write its images — in their slack while the laggards finish the v block.  Last, every wave runs Adam
-// on the vector entries it owns (the 648 bias / LayerNorm elements, at most 2 per thread): an entry belongs to the
+// blocks) and write its images — in their slack while the laggards finish the v block.  Inside those Adam passes
+// (laggards: the v unit's, leaders: the small unit's) every wave also runs Adam on the vector entries it owns (the
+// 648 bias / LayerNorm elements, at most 2 per thread, profiles/ab_tf2_frag_pipeline.log): an entry belongs to the
 // thread whose registers hold its gradient sum — a column of one of the wave's all-ones MFMA accumulators, or the
 // LayerNorm accumulator the thread reads (vec_entry) — so nothing is staged through LDS and the only barrier after
 // the units is the step's end barrier.  (Before, the sums went to an fp32 staging array behind one barrier and
@@ -823,12 +954,12 @@ __device__ __forceinline__ bool br_update(uchar* smem, BrState& st, const AdamK&
   const int Ta = 2 * (w4 & 1), Tb = 2 * (w4 >> 1);
   const bool do_bias = (w4 & 1) == 0;  // one of the two units that read dY tiles Tb, Tb + 1
   f4v bsu[2] = {Z4, Z4};               // the unit's bias sums (out_proj on leaders, v on laggards)
-  f4v cmom;                            // the compact entries' moments m0 m1 v0 v1
   f4v as = Z4, bd = Z4, a3 = Z4, af1 = Z4, b3 = Z4, b1 = Z4;  // leaders: dense / ffn.3 / ffn.0 tiles + bias sums
   const int ui = 2 * w4 + (lead ? 0 : 1);
   f4v U[12];
 #pragma unroll
   for (int j = 0; j < 12; ++j) U[j] = unit_ld(rm, ui, j, lane);
+  const f4v cmom = mom_ld(rm, 0, tid);  // the vector entries' moments m0 m1 v0 v1 (in flight over the waits below)
   uint32_t o1 = 0x3F803F80u;  // (all-ones operand, opaque SGPR: see unit_dw)
   asm volatile("" : "+s"(o1));
   const s8v one = __builtin_bit_cast(s8v, u32x4{o1, o1, o1, o1});
@@ -868,27 +999,63 @@ __device__ __forceinline__ bool br_update(uchar* smem, BrState& st, const AdamK&
     if (any) return false;
   }
   stp(4, tid);
+  // ---- the vector entries (648 bias / LayerNorm elements), owner-computed: every gradient sum ends in a register of
+  // the thread that owns the entry (vec_entry) — the bias sums in the all-ones MFMA accumulators, the LayerNorm sums
+  // read here from the fp64 accumulators.  Those are complete at counter A, which this wave has passed: every
+  // ln_colsum of br_backward precedes its wave's lds_signal(B_CNT_A), and the signal drains the wave's LDS operations
+  // first; the backward's last VEC read (gamma1) precedes that signal too, so from here on an owner may write its VEC
+  // words.  The slot is zeroed by its reader and added to again only after the step's end barrier.  The entries'
+  // Adam rides in the stages of a unit's Adam (laggards: unit_adam, whose v bias sums exist after unit_dw; leaders:
+  // smu_adam, right after their last input, the dense bias sums) as two more independent chains, and each owner
+  // writes its VEC words next to the unit's image: no staging, no barrier, no dependent chain of its own at the end
+  // of the step (it cost every wave ~0.4 us there).  Threads without an entry compute on zeros and store nothing.
+  VecAd x;
+  x.g[0] = b1[0];
+  if (wave >= 2) {
+    LDS_AS double* q = (LDS_AS double*)(smem + B_DBL) + 64 * (wave - 2) + lane;
+    x.g[0] = lds_getq(smem + B_DBL, 64 * (wave - 2) + lane);
+    *q = 0.0;
+  }
+  auto vec_in = [&]() {  // (once the wave's bias sums exist)
+    x.g[1] = g == 0 ? bsu[0][0] : g == 1 ? bsu[1][0] : g == 2 ? b3[0] : bd[0];
+    x.m[0] = cmom[0], x.m[1] = cmom[1], x.v[0] = cmom[2], x.v[1] = cmom[3];
+  };
+  auto vec_out = [&]() {
+#pragma unroll
+    for (int h = 0; h < NCMP; ++h) {
+      // (a few VALU per step: kept as per-thread state the two offsets spill, in two register classes and in one:
+      // profiles/ab_tf2_tail.log, profiles/ab_tf2_regs.log)
+      const int e = vec_entry(wave, lane, h);
+      if (vec_real(e)) ldsf(smem, B_VEC)[e] = x.pn[h];
+    }
+  };
   {  // the unit: out_proj (leaders: X = a, dY = d o) or in_proj.v (laggards: X = h0, dY = d v)
     f4v acc[2][2];
     if (!ABL(K, ABL_UDW))
       unit_dw(smem + (lead ? B_A : B_H0), smem + (lead ? B_DO : B_DV), Ta, Tb, lane, do_bias, acc, bsu);
-    if (!ABL(K, ABL_UADAM)) unit_adam(U, acc, K);
+    if (!lead) {
+      vec_in();
+      if (!ABL(K, ABL_UADAM)) unit_adam<NCMP>(U, acc, K, st.cmp, x);
+    } else {
+      if (!ABL(K, ABL_UADAM)) unit_adam<0>(U, acc, K, st.cmp, x);
+    }
     u32x2v w[4];
     unit_pack(U, w);
-    cmom = mom_ld(rm, 0, tid);  // (issued here: in flight over the wait for B, the image and the unit's stores)
     if (!lead && !lds_wait(smem, B_CNT_B, all)) {  // (the v image is read until the end of every wave's backward)
       if (lane == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       return false;
     }
     unit_img(smem, B::vo(!lead), Ta, Tb, lane, w);
+    if (!lead && !ABL(K, ABL_UADAM)) vec_out();
 #pragma unroll
     for (int j = 0; j < 12; ++j) unit_st(rm, ui, j, lane, U[j]);
+    if (!lead) mom_st(rm, 0, tid, f4v{x.m[0], x.m[1], x.v[0], x.v[1]});
   }
   if (lead) {
     f4v S[9];  // the small unit (issued here: its loads overlap the wait for B and the dense MFMAs)
 #pragma unroll
     for (int j = 0; j < 9; ++j) S[j] = smu_ld(rm, w4, j, lane);
-    if (!lds_wait(smem, B_CNT_B, all)) {  // (the dense dY rows and the LayerNorm sums below are complete at B)
+    if (!lds_wait(smem, B_CNT_B, all)) {  // (the dense dY rows are complete at B)
       if (lane == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       return false;
     }
@@ -901,40 +1068,14 @@ __device__ __forceinline__ bool br_update(uchar* smem, BrState& st, const AdamK&
     // Adam on the small unit (dense, ffn.3, ffn.0 tiles); their images are free: the dense one is read only by the
     // forward, the ffn ones by the backward before counters C / A
     const f4v gs3[3] = {as, a3, af1};
-    if (!ABL(K, ABL_U3)) smu_adam(S, gs3, K);
+    vec_in();
+    if (!ABL(K, ABL_U3)) smu_adam<NCMP>(S, gs3, K, st.cmp, x);
     smu_img<BR>(smem, S, w4, lane);
+    if (!ABL(K, ABL_U3)) vec_out();
 #pragma unroll
     for (int j = 0; j < 9; ++j) smu_st(rm, w4, j, lane, S[j]);
+    mom_st(rm, 0, tid, f4v{x.m[0], x.m[1], x.v[0], x.v[1]});
   }
-  // ---- the vector entries (648 bias / LayerNorm elements), owner-computed: every gradient sum is already in a
-  // register of the thread that owns the entry (vec_entry) — the bias sums in the all-ones MFMA accumulators, the
-  // LayerNorm sums read here from the fp64 accumulators (complete at counter B, which every wave has passed) — so
-  // Adam runs on them at once and each owner writes its VEC words itself.  No staging, no barrier: VEC is read
-  // again only by the next forward, after the end barrier; the accumulator slot is zeroed by its reader and
-  // added to again only after that barrier.  Threads without an entry compute on zeros and store nothing.
-  stp(5, tid);
-  prio_hi();
-  float gr[NCMP];
-  gr[0] = b1[0];
-  if (wave >= 2) {
-    LDS_AS double* q = (LDS_AS double*)(smem + B_DBL) + 64 * (wave - 2) + lane;
-    gr[0] = lds_getq(smem + B_DBL, 64 * (wave - 2) + lane);
-    *q = 0.0;
-  }
-  gr[1] = g == 0 ? bsu[0][0] : g == 1 ? bsu[1][0] : g == 2 ? b3[0] : bd[0];
-  float mm[NCMP] = {cmom[0], cmom[1]}, vv[NCMP] = {cmom[2], cmom[3]};
-  if (!ABL(K, ABL_U3)) {
-    float pn[NCMP];
-    vec_adam<NCMP>(st.cmp, mm, vv, gr, pn, K);
-#pragma unroll
-    for (int h = 0; h < NCMP; ++h) {
-      // (a few VALU per step: kept as per-thread state the two offsets spill, in two register classes and in one:
-      // profiles/ab_tf2_tail.log, profiles/ab_tf2_regs.log)
-      const int e = vec_entry(wave, lane, h);
-      if (vec_real(e)) ldsf(smem, B_VEC)[e] = pn[h];
-    }
-  }
-  mom_st(rm, 0, tid, f4v{mm[0], mm[1], vv[0], vv[1]});
   return true;
 }
 
@@ -1124,7 +1265,7 @@ __device__ __forceinline__ void branch_main(const AflTfTrainArgs& a, int cid, uc
 #endif
     asm volatile(";MARK fwd_end");
     stp(0, tid);
-    gr_put(rg, gr_off(0, BR, wave, lane), outp, (uint32_t)step);  // this wave's output rows -> head
+    gr_put_s(rg, gr_soff(0, BR, wave), 16 * lane, outp, (uint32_t)step);  // this wave's output rows -> head
     prio_lo();
     w.b0 += BS;  // prefetch the next batch's inputs while the head works
     more = walk_valid(w, nd, BS, E);
@@ -1141,8 +1282,8 @@ __device__ __forceinline__ void branch_main(const AflTfTrainArgs& a, int cid, uc
     sb();
     stp(1, tid);
     u32x4 du[2];
-    const int go[1] = {gr_off(1, BR, wave, lane)};
-    const uint32_t fv = gr_get<1>(rg, go, du, (uint32_t)step, 1, sync + XF_TMO, lane);  // d(out) of this wave's rows
+    const int go[1] = {gr_soff(1, BR, wave)};
+    const uint32_t fv = gr_get_s<1>(rg, go, 16 * lane, du, (uint32_t)step, 1, sync + XF_TMO, lane);  // d(out) of this wave's rows
     prio_hi();  // (the leaders' backward below the laggards' measured -0.5 %: profiles/ab_tf2_r6_update.log)
     stp(2, tid);
     if (fv == 0xFFFFFFFFu) {  // timed out: abort the step for every wave (they wait on this wave's progress)
@@ -1176,9 +1317,9 @@ __device__ __forceinline__ void branch_main(const AflTfTrainArgs& a, int cid, uc
       failed = true;
       break;
     }
-    stp(7, tid);
+    stp(5, tid);
     lds_bar();
-    stp(8, tid);
+    stp(6, tid);
   }
   (void)failed;
   stamp_fini(stp, a, smem, tid);

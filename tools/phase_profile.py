@@ -30,8 +30,8 @@ NAMES = {0: "F:G1 dense+E1", 1: "F:G2 vproj+E2", 2: "F:G3 oproj+E3 LN1", 3: "F:G
 # 11 = import of the partner's rows.
 NAMES4 = {0: "B:forward", 1: "B:publish+prefetch+masks+backward prologue", 2: "B:wait d(out)", 3: "B:backward",
           4: "B:leaders ffn tiles + wait counter A / laggards wait counter A, abort",
-          5: "B:units (leaders out_proj + dense + small-unit Adam / laggards in_proj.v)",
-          7: "B:vector Adam (owner-computed, no barrier)", 8: "B:end barrier", 10: "H:wait branches",
+          5: "B:units with the vector Adam in their stages (leaders out_proj + dense + small-unit Adam / laggards in_proj.v)",
+          6: "B:end barrier", 10: "H:wait branches",
           11: "H:fwd+loss+bwd+publish+export", 12: "H:bar+loss", 13: "H:dW+Adam", 14: "H:end barrier"}
 
 def block_stride(clients: int, wgs: int, dev) -> int:
