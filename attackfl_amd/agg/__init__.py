@@ -17,6 +17,7 @@ Each rule returns ``AggResult(params [P] | None, ok, info)``.  Rows are in clien
 * byzantine     ``src/Utils.py:218-248`` (dead code in the reference) cosine ≥ 0.9 to model 0
 Beyond the reference (docs/PARITY.md): multi_krum, bulyan, dnc (assumed Byzantine count ``byz-f``), geomed (RFA) and
 cclip (centred clipping about the global model the round started from: the one rule that takes ``centre``).
+Pre-aggregation in front of a rule (engine ``pre-agg``): ``nnm`` (nearest-neighbour mixing) and ``bucketing``.
 FLTrust and the hypernetwork live in the engine (``fl/engine.py`` ``_fltrust``, ``fl/hyper_server.py``): they train.
 """
 from __future__ import annotations
@@ -28,7 +29,7 @@ from typing import Dict, Optional, Union
 import torch
 
 from .. import ops
-from ..config import KNOB  # (a rule knob's default and check: stated once, in config.RULE_KNOBS)
+from ..config import BUCKET_SIZE, KNOB, PRE_AGG_KINDS  # (a knob's default and check: stated once, in config)
 from ..ops.composite import gmm_filter_ref  # noqa: F401  (the kernel's host mirror: tools and tests import it here)
 
 
@@ -52,10 +53,13 @@ def mean_of(U: torch.Tensor) -> torch.Tensor:
 
 def host_info(info: Dict) -> Dict:
     """An aggregator's info with device values read back (the engine calls it where the host waits anyway,
-    after validation): bool masks become index lists, 0-d tensors numbers, vectors lists."""
+    after validation): bool masks become index lists, 0-d tensors numbers, vectors lists; a nested dict
+    (``pre_agg``) likewise."""
     out = {}
     for k, v in info.items():
-        if torch.is_tensor(v):
+        if isinstance(v, dict):
+            v = host_info(v)
+        elif torch.is_tensor(v):
             v = v.cpu()
             if v.dtype == torch.bool:
                 v = torch.nonzero(v).reshape(-1).tolist() if v.dim() else bool(v)
@@ -289,6 +293,46 @@ def byzantine(U: torch.Tensor, sizes=None, threshold: float = 0.9, **_) -> AggRe
     """Cosine >= 0.9 to model 0, mean of the kept rows (all rows when none passes), on the device."""
     keep = ops.cosine_to(U, U[0], eps=1e-8) >= threshold
     return AggResult(_masked_mean(U, keep), True, {"kept": keep})
+
+
+# ---------------------------------------------------------------------------------- pre-aggregation
+# In front of a robust rule (engine ``pre-agg``; rule text in docs/PARITY.md): (U, sizes) -> (Y, sizes', info), the
+# rule then runs on (Y, sizes') with its usual keywords.  Both are one row mix Y = W U (``ops.mix_rows``: one pass
+# over U on the device); neither reads a device value back; ``U`` stays read-only.
+def nnm(U: torch.Tensor, sizes=None, byz_f=KNOB["byz_f"].default):
+    """Nearest-neighbour mixing (Allouah et al., AISTATS 2023): every row becomes the unweighted mean of its n - f
+    nearest rows by (squared distance, index), itself included; f as Multi-Krum takes it (``byz-f``, n >= 2 f + 3).
+    ``sizes`` passes through.  Device, n <= 64: the Gram-form distances, ``k_nnm_weights``, ``k_mix_rows``.  f = 0
+    gives n copies of the mean, by the same three steps."""
+    n = U.shape[0]
+    f = byzantine_count(n, byz_f, 2, "nnm")
+    W, _ = ops.nnm_weights(ops.pairwise_sqdist(U), f)
+    return ops.mix_rows(W, U), sizes, {"kind": "nnm", "f": f, "weights": W, "rows": n}
+
+
+def bucketing(U: torch.Tensor, sizes=None, bucket_size=BUCKET_SIZE.default, seed: int = 0):
+    """Bucketing (Karimireddy, He & Jaggi, ICLR 2022): the rows shuffled by the permutation of (seed, n) and averaged,
+    size-weighted, in buckets of ``bucket_size`` (the last one may be short) -> the R = ceil(n / bucket_size) bucket
+    means and the buckets' size sums (in ``sizes``' dtype, where it lives; fp64 counts when it is None).
+    ``bucket_size`` 1 returns ``U`` and ``sizes`` themselves."""
+    n = U.shape[0]
+    s = BUCKET_SIZE.check(bucket_size)
+    if s == 1:
+        return U, sizes, {"kind": "bucketing", "bucket_size": 1, "rows": n,
+                          "weights": torch.eye(n, dtype=torch.float64, device=U.device)}
+    W, tot = ops.composite.bucket_weights(sizes, n, s, seed)
+    return (ops.mix_rows(W, U), tot if sizes is None else tot.to(sizes.dtype),
+            {"kind": "bucketing", "bucket_size": s, "weights": W, "rows": int(W.shape[0])})
+
+
+def pre_aggregate(kind: str, U: torch.Tensor, sizes=None, byz_f=KNOB["byz_f"].default,
+                  bucket_size=BUCKET_SIZE.default, seed: int = 0, **_):
+    """``nnm`` or ``bucketing`` by name, each taking its own keywords -> (Y, sizes', info)."""
+    if kind == "nnm":
+        return nnm(U, sizes, byz_f)
+    if kind == "bucketing":
+        return bucketing(U, sizes, bucket_size, seed)
+    raise ValueError(f"pre-aggregation '{kind}' is not valid (choose from {PRE_AGG_KINDS[1:]}).")
 
 
 # Contract of every aggregator: ``U`` is READ-ONLY and may be the live client-model rows (single rank: the

@@ -63,6 +63,13 @@ Extensions (all optional, defaults keep reference behaviour):
   cclip-iters: int >= 1             (cclip: clipping iterations, all of them run, default 3; 1 = norm bounding)
   cclip-tau: auto | float > 0       (cclip: the clipping radius; auto, the default = the lower median of the rows'
                                     distances to the round's starting model, found on the device every round)
+  pre-agg: none | nnm | bucketing   (pre-aggregation in front of the rule of ``server.mode``, docs/PARITY.md; default
+                                    none.  nnm: every row becomes the mean of its n - f nearest rows, itself included
+                                    (f from byz-f, needs n >= 2 f + 3 when explicit); bucketing: the rows are shuffled
+                                    with the round's seed and averaged in buckets of bucket-size, and the rule, its
+                                    byz-f ``auto`` and its admissibility checks then see the ceil(n / bucket-size)
+                                    bucket means.  Refused for fedavg, hyper, FLTrust and gmm)
+  bucket-size: int >= 1             (bucketing: rows per bucket, default 2; 1 leaves the rows as they are)
   save-state: bool                  (write {model}.state.pt + {model}.clients.r{rank}.pt every round)
   resume: bool                      (continue from those files: counters, RNGs, optimizer moments)
 """
@@ -175,6 +182,12 @@ RULE_KNOBS = (  # engine key, rule keyword, kind, default, lo, auto  (what each 
 )
 KNOB = {k.kw: k for k in RULE_KNOBS}
 
+# pre-aggregation in front of a robust rule (``engine.pre-agg``; docs/PARITY.md): not rule knobs, the rules never see them
+PRE_AGG_KINDS = ("none", "nnm", "bucketing")
+# FedAvg has its own fused and all-reduce paths, the hypernetwork and FLTrust train, gmm reads per-row attacker flags
+PRE_AGG_REFUSED_MODES = ("fedavg", "hyper", "FLTrust", "gmm")
+BUCKET_SIZE = RuleKnob("bucket-size", "bucket_size", "int", 2, 1)
+
 EXTENSION_DEFAULTS: Dict[str, Any] = {
     "comm": {"backend": "auto", "address": "", "port": 29517, "clients-per-rank": 0, "one-shot-allgather": "auto",
              "fedavg-allreduce": "auto", "timeout-s": 600, "attackers": {}},
@@ -184,7 +197,7 @@ EXTENSION_DEFAULTS: Dict[str, Any] = {
                "async-checkpoint": True, "compat-hyper-resume": False, "compat-fltrust": False, "max-retries": 50, "trace": False,
                "phase-sync": False, "fault-inject": [], "save-state": False, "resume": False,
                "speculative": True, "compat-har-train": False, "compat-fedavg-alias": False,
-               **{k.key: k.default for k in RULE_KNOBS}},
+               **{k.key: k.default for k in RULE_KNOBS}, "pre-agg": "none", BUCKET_SIZE.key: BUCKET_SIZE.default},
 }
 
 
@@ -349,6 +362,13 @@ class Config:
             raise ValueError("engine.distance must be 'spectral' or 'flat'")
         for k in RULE_KNOBS:
             k.check(self.engine.get(k.key, k.default), "engine.")
+        pre = self.engine.get("pre-agg", "none")
+        if not isinstance(pre, str) or pre not in PRE_AGG_KINDS:
+            raise ValueError(f"engine.pre-agg must be one of {PRE_AGG_KINDS} (got {pre!r})")
+        BUCKET_SIZE.check(self.engine.get(BUCKET_SIZE.key, BUCKET_SIZE.default), "engine.")
+        if pre != "none" and self.mode in PRE_AGG_REFUSED_MODES:
+            raise ValueError(f"engine.pre-agg: {pre} does not apply to server.mode '{self.mode}' (it goes in front of "
+                             f"a robust rule; not {', '.join(PRE_AGG_REFUSED_MODES)})")
         return self
 
     def to_dict(self) -> Dict[str, Any]:

@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..agg import AGGREGATORS, AggResult
+from ..agg import AGGREGATORS, AggResult, pre_aggregate
 from ..agg import host_info as agg_host_info
 from ..attacks import DistanceEngine, host_info, run_attack
 from ..config import RULE_KNOBS, AttackSpec, Config
@@ -808,7 +808,8 @@ class FLEngine:
         ``enable``; FedAvg also takes the clients' int32 success flags themselves and reduces them inside its own
         pass.  ``w``: FedAvg weights already on the device (each caller keeps its own source); ``gen_key``: the clients
         whose next START models the hypernetwork update generates.  Returns (info, the rule's own success: None =
-        always, or a 0-d tensor — gmm).  What a failed early round rolls back stays on ``self`` (``fltrust_model``,
+        always, or a 0-d tensor — gmm).  ``engine.pre-agg`` (nnm, bucketing: ``agg.pre_aggregate``) goes in front of a
+        rule of AGGREGATORS on either path.  What a failed early round rolls back stays on ``self`` (``fltrust_model``,
         ``_trust``, ``_fl_pending``, ``hyper.step``: ``_early_launch_failed``)."""
         mode, g_old = self.mode, self.global_params
         if mode == "hyper":
@@ -830,8 +831,15 @@ class FLEngine:
             else:
                 self.global_params = torch.where(ok_all, ops.weighted_rows(U, w), g_old)
             return {"n": int(U.shape[0])}, None
-        res: AggResult = AGGREGATORS[mode](U, sizes, attackers=attackers, **self._rule_args())
+        args, pre = self._rule_args(), None
+        if self.cfg.engine.get("pre-agg", "none") != "none":
+            # (device work without a host read, like the rules: the rule then sees the mixed rows and their sizes)
+            U, sizes, pre = pre_aggregate(self.cfg.engine["pre-agg"], U, sizes, byz_f=args["byz_f"], seed=args["seed"],
+                                          bucket_size=self.cfg.engine.get("bucket-size", 2))
+        res: AggResult = AGGREGATORS[mode](U, sizes, attackers=attackers, **args)
         info = {k: v for k, v in res.info.items() if k != "scores"}
+        if pre is not None:
+            info["pre_agg"] = pre
         if ok_all is None:
             if not bool(res.ok):  # (gmm on the device: a 0-d tensor, the serial path's one synchronising read)
                 info["agg_failed"] = True
@@ -1284,7 +1292,7 @@ class FLEngine:
         info = agg_host_info(info)  # (device-resident aggregator outputs: read now, after validation)
         if self._trust is not None:
             info["trust"] = [round(float(x), 6) for x in self._trust.tolist()]
-        rec.update({k: v for k, v in info.items() if isinstance(v, (int, float, list, str))})
+        rec.update({k: v for k, v in info.items() if isinstance(v, (int, float, list, str)) or k == "pre_agg"})
         losses = self._client_losses(meta)
         if losses is not None:
             rec["client_loss"] = losses

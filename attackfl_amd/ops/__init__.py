@@ -311,6 +311,29 @@ def krum_select(D: torch.Tensor, f: int, rounds: int, iterated: bool):
     return composite.krum_select(D, int(f), int(rounds), bool(iterated))
 
 
+def mix_rows(W: torch.Tensor, U: torch.Tensor) -> torch.Tensor:
+    """Y [R, P] = W U for a small dense W [R, n] (fp64) and rows U [n, P] (fp32): pre-aggregation's row mix, fp64
+    accumulation in ascending j over every j.  Device, n <= 64 and R <= 64: ``k_mix_rows``, one pass over U, every
+    Y[r] the bits of ``weighted_rows(U, W[r])``; a host W goes up pinned.  The composite beyond."""
+    if _dev(U):
+        from .layers import upload
+
+        W = W.to(torch.float64)
+        W = W if W.is_cuda else upload(W, U.device)
+        if 1 <= U.shape[0] <= 64 and 1 <= W.shape[0] <= 64:
+            return native().mix_rows(W.contiguous(), U.to(torch.float32).contiguous())
+    return composite.mix_rows(W, U)
+
+
+def nnm_weights(D: torch.Tensor, f: int):
+    """Nearest-neighbour mixing's weights on the squared-distance matrix -> (W [n, n] fp64, the neighbour sets [n] as
+    int64 bit masks).  Device, n <= 64: ``k_nnm_weights`` (one launch, no host read); the composite beyond."""
+    if _dev(D) and D.shape[0] <= 64:
+        W, nbr = native().nnm_weights(D.to(torch.float64).contiguous(), int(f))
+        return W, nbr
+    return composite.nnm_weights(D, int(f))
+
+
 def agr_bisect_fused(Dg: torch.Tensor, A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, m: int, f: int, target: str,
                      n_iter: int, gamma: float) -> Optional[torch.Tensor]:
     """The AGR-tailored bisection as ONE launch (``agg.hip`` ``k_agr_bisect``) -> the state ``st [40]`` fp64 (st[1] last

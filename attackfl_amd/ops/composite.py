@@ -156,6 +156,59 @@ def krum_select(D: torch.Tensor, f: int, rounds: int, iterated: bool):
     return torch.stack(sel), ~active, first
 
 
+# ---------------------------------------------------------------- pre-aggregation (docs/PARITY.md)
+def mix_rows(W: torch.Tensor, U: torch.Tensor) -> torch.Tensor:
+    """Y = W U for a small dense W [R, n] (fp64) and rows U [n, P] (``agg.hip`` ``k_mix_rows``): an fp64 sum in
+    ascending j over every j, zero weights included (a non-finite row poisons every mixed row), rounded to fp32 once.
+    Tensor ops only, so it also serves device tensors beyond the kernel's 64 rows."""
+    W = W.to(device=U.device, dtype=torch.float64)
+    acc = torch.zeros(W.shape[0], U.shape[1], dtype=torch.float64, device=U.device)
+    for j in range(U.shape[0]):
+        acc += W[:, j, None] * U[j].double()[None, :]
+    return acc.to(torch.float32)
+
+
+def nnm_weights(D: torch.Tensor, f: int):
+    """Nearest-neighbour mixing's W [n, n] fp64 from the squared distances ``D [n, n]`` (``agg.hip`` ``k_nnm_weights``):
+    D read as symmetric from its upper triangle, a NaN entry as +inf; row i mixes itself and the first n - f - 1 other
+    rows by (D_ij, j) ascending with weight 1 / (n - f) each.  -> (W, the neighbour sets [n] as int64 bit masks).
+    Tensor ops only (no host read)."""
+    n = D.shape[0]
+    D = torch.triu(D.double(), 1)
+    D = D + D.t()
+    key = torch.where(torch.isnan(D), torch.full_like(D, float("inf")), D)
+    order = torch.sort(key, dim=1, stable=True).indices
+    idx = torch.arange(n, device=D.device)
+    other = order != idx[:, None]
+    take = other & (torch.cumsum(other, dim=1) <= n - f - 1)
+    member = torch.zeros(n, n, dtype=torch.bool, device=D.device).scatter_(1, order, take) | (idx[:, None] == idx[None, :])
+    W = member.double() * (1.0 / (n - f))
+    return W, (member.long() << idx[None, :]).sum(dim=1)
+
+
+def bucket_permutation(seed: int, n: int) -> torch.Tensor:
+    """Bucketing's shuffle: the row indices sorted by (u_i, i), u = ``afl_uniform(seed, n)`` (host, int64)."""
+    return torch.sort(afl_uniform(seed, n), stable=True).indices
+
+
+def bucket_weights(sizes: Optional[torch.Tensor], n: int, s: int, seed: int):
+    """Bucketing's W [R, n] fp64, R = ceil(n / s): bucket r = pi[r s : (r + 1) s] of ``bucket_permutation``,
+    W_rj = sizes_j / (the bucket's size sum) for j in bucket r (uniform when ``sizes`` is None).  -> (W, the buckets'
+    size sums [R] fp64), both where ``sizes`` lives (the host when None): pi depends on (seed, n) only and goes up
+    pinned; no device value is read back."""
+    from .layers import upload
+
+    pi = bucket_permutation(seed, n)
+    R = -(-n // s)
+    bucket = torch.empty(n, dtype=torch.int64)
+    bucket[pi] = torch.arange(n, dtype=torch.int64) // s
+    a = torch.ones(n, dtype=torch.float64) if sizes is None else sizes.to(torch.float64)
+    member = upload(bucket[None, :] == torch.arange(R, dtype=torch.int64)[:, None], a.device)
+    M = member.double() * a[None, :]
+    tot = M.sum(dim=1)
+    return M / tot[:, None], tot
+
+
 AGR_TARGETS = ("krum", "mkrum", "bulyan")  # (the kernel's target 0 / 1 / 2)
 
 

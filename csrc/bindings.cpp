@@ -196,6 +196,36 @@ std::vector<torch::Tensor> krum_select(torch::Tensor D, int64_t f, int64_t round
   return {sel, mask, scores};
 }
 
+// Pre-aggregation's row mix (agg.nnm / agg.bucketing): W [R, N] fp64, U [N, P] fp32 -> Y [R, P] fp32 in one pass over U
+torch::Tensor mix_rows(torch::Tensor W, torch::Tensor U) {
+  check_dev(W, "W", torch::kFloat64);
+  check_dev(U, "U", torch::kFloat32);
+  TORCH_CHECK(W.dim() == 2 && U.dim() == 2 && W.size(1) == U.size(0) && W.get_device() == U.get_device(),
+              "mix_rows: W [R, N] and U [N, P] on one device");
+  const int64_t R = W.size(0), N = U.size(0), P = U.size(1);
+  TORCH_CHECK(R >= 1 && R <= 64 && N >= 1 && N <= 64 && P >= 1, "mix_rows: 1 <= R, N <= 64 and P >= 1 (got R = ", R,
+              ", N = ", N, ", P = ", P, ")");
+  auto Y = torch::empty({R, P}, U.options());
+  TORCH_CHECK(afl_mix_rows(U.data_ptr<float>(), W.data_ptr<double>(), (int)N, (int)R, P, Y.data_ptr<float>(), cur()) == 0,
+              "mix_rows launch failed");
+  AFL_CHECK_LAUNCH();
+  return Y;
+}
+
+// Nearest-neighbour mixing's weights (agg.nnm): D [n, n] fp64 -> (W [n, n] fp64, neighbour sets [n] int64 bit masks)
+std::vector<torch::Tensor> nnm_weights(torch::Tensor D, int64_t f) {
+  check_dev(D, "D", torch::kFloat64);
+  const int64_t n = check_square64(D, "nnm_weights: D [n, n], n <= 64");
+  TORCH_CHECK(f >= 0 && f <= n - 1, "nnm_weights: n = ", n, " needs 0 <= f <= n - 1 (got f = ", f, ")");
+  auto W = torch::empty({n, n}, D.options());
+  auto nbr = torch::empty({n}, D.options().dtype(torch::kInt64));
+  TORCH_CHECK(afl_nnm_weights(D.data_ptr<double>(), (int)n, (int)f, W.data_ptr<double>(),
+                              reinterpret_cast<unsigned long long*>(nbr.data_ptr<int64_t>()), cur()) == 0,
+              "nnm_weights launch failed");
+  AFL_CHECK_LAUNCH();
+  return {W, nbr};
+}
+
 // AGR-tailored bisection (attacks AGR-Krum / AGR-MKrum / AGR-Bulyan): st [40] fp64 with st[0] = gamma0, Dg [K, K],
 // A / B [K], C scalar, all fp64 on one device; the trace lands in st.  Refused here, before any launch, when the
 // modelled system does not fit the kernel or the rule.
@@ -1009,6 +1039,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gmm_filter", &gmm_filter, pybind11::arg("G"), pybind11::arg("att"), pybind11::arg("rank") = 0);
   m.def("top_pc", &top_pc);
   m.def("krum_select", &krum_select);
+  m.def("mix_rows", &mix_rows);
+  m.def("nnm_weights", &nnm_weights);
   m.def("agr_bisect", &agr_bisect);
   m.def("dnc_run", &dnc_run);
   m.def("bulyan_coord", &bulyan_coord);

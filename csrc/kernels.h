@@ -459,6 +459,13 @@ int afl_top_pc(const double* G, int n, int sweeps, double* z, hipStream_t s);
 // Bulyan) -> sel [rounds] int32 in selection order, mask [n] 0/1, scores [n] fp64 of the first pass
 int afl_krum_select(const double* D, int n, int f, int rounds, int iterated, int* sel, unsigned char* mask,
                     double* scores, hipStream_t s);
+// Pre-aggregation (docs/PARITY.md).  afl_mix_rows (agg.hip k_mix_rows): Y [R][P] = W U for W [R][N] fp64 and U [N][P]
+// fp32 in one pass over U, every Y[r] the bits of afl_weighted_rows(U, W[r]); 1 <= N, R <= 64.  afl_nnm_weights
+// (k_nnm_weights): nearest-neighbour mixing's W [n][n] = 1 / (n - f) on row i's n - f nearest rows (itself included) by
+// (D_ij, j), D [n][n] fp64 read from its upper triangle, NaN as +inf; nbr [n] the neighbour sets as 64-bit masks.
+// hipErrorInvalidValue unless 1 <= n <= 64 and 0 <= f <= n - 1.
+int afl_mix_rows(const float* U, const double* W, int N, int R, long P, float* Y, hipStream_t s);
+int afl_nnm_weights(const double* D, int n, int f, double* W, unsigned long long* nbr, hipStream_t s);
 // AGR-tailored bisection (agg.hip k_agr_bisect; attacks AGR-Krum / AGR-MKrum / AGR-Bulyan, docs/PARITY.md): K genuine
 // rows with squared distances Dg [K][K] fp64 plus m copies of mean - gamma dev at squared distance
 // max(A_j - 2 gamma B_j + gamma^2 C, 0); target 0 Krum, 1 Multi-Krum, 2 Bulyan with the assumed Byzantine count f; n_iter

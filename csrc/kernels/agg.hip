@@ -2,6 +2,8 @@
 //
 //   colstats        column mean / unbiased std (+ LIE candidate mean + z*std)      K-G2/K-G3
 //   weighted_rows   out = sum_i w_i U_i (fp64 weights, fp64 accumulate)            K-G1 FedAvg
+//   mix_rows        Y = W U, W [R][N] fp64, one pass over U (pre-aggregation: NNM, bucketing; beyond the reference)
+//   nnm_weights     nearest-neighbour mixing's W from the distance matrix, one wave (the row sort of krum_select)
 //   pair_sqdist     D2[i][j] = ||U_i - U_j||^2 (fp64 difference form, no cancellation) K-G4b / Krum (K > 64)
 //   gram_f64        the same from the Gram matrix of the rows centred on a robustly  K-G4b / Krum (K <= 64)
 //                   chosen row, on fp64 MFMA
@@ -60,6 +62,10 @@ void afl_colstats(const float* G, int K, long P, float* mean, float* stdv, float
 }
 
 // ============================================================================ weighted rows
+// The accumulate step of weighted_rows and mix_rows, stated once (an explicit fma, which is what the contracted
+// acc += w * u compiled to): a mixed row carries the bits of the weighted_rows call with that row of weights.
+__device__ __forceinline__ double row_acc(double acc, double w, double u) { return fma(w, u, acc); }
+
 // ok (optional, int32 [N]): every entry > 0 -> the weighted sum, else out = fallback (FedAvg keeps the previous global
 // model when a client failed: the early-launch aggregate, decided on the device in the same pass)
 __global__ void __launch_bounds__(256) k_weighted_rows(const float* __restrict__ U, const double* __restrict__ w, int N,
@@ -75,13 +81,59 @@ __global__ void __launch_bounds__(256) k_weighted_rows(const float* __restrict__
     return;
   }
   double acc = 0.0;
-  for (int i = 0; i < N; ++i) acc += w[i] * (double)U[(long)i * P + c];
+  for (int i = 0; i < N; ++i) acc = row_acc(acc, w[i], (double)U[(long)i * P + c]);
   out[c] = (float)acc;
 }
 
 void afl_weighted_rows(const float* U, const double* w, int N, long P, float* out, hipStream_t s, const int* ok,
                        const float* fallback) {
   hipLaunchKernelGGL(k_weighted_rows, dim3(afl_cdiv(P, 256)), dim3(256), 0, s, U, w, N, P, out, ok, fallback);
+}
+
+// ============================================================================ mix rows
+// Y = W U for a small dense W [R][N] (fp64) in ONE pass over U [N][P]: the row mix of pre-aggregation (nearest-neighbour
+// mixing, bucketing; docs/PARITY.md).  Thread per column: the column's N values sit in registers (as the doubles the
+// accumulate step takes: the conversion is exact and is paid once, not once per mixed row), then for every r an fp64
+// dot in ascending j over every j (zero weights included, as weighted_rows does) and a coalesced store of Y[r][c].
+// W is staged once per block in LDS (R * NMAX doubles, at most 32 KB); every lane reads the same entry, a broadcast.
+// N <= NMAX <= 64, R <= 64.  The dot is unrolled over all NMAX terms without a branch: a term j >= N is W = -0.0 times
+// value +0.0, and adding that -0.0 returns every accumulator unchanged, a zero of either sign included, so Y[r] is the
+// bits of weighted_rows(U, W[r]) for every N.
+template <int NMAX>
+__global__ void __launch_bounds__(256) k_mix_rows(const float* __restrict__ U, const double* __restrict__ W, int N, int R,
+                                                  long P, float* __restrict__ Y) {
+  extern __shared__ double mix_w[];  // [R][NMAX]
+  for (int e = threadIdx.x; e < R * NMAX; e += 256) {
+    const int r = e / NMAX, j = e - r * NMAX;
+    mix_w[e] = j < N ? W[r * N + j] : -0.0;
+  }
+  __syncthreads();
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long cc = c < P ? c : P - 1;  // (a thread past the last column mixes that column again and stores nothing)
+  double v[NMAX];
+#pragma unroll
+  for (int j = 0; j < NMAX; ++j) {
+    const float u = U[(long)(j < N ? j : N - 1) * P + cc];
+    v[j] = j < N ? (double)u : 0.0;
+  }
+  for (int r = 0; r < R; ++r) {
+    const double* w = mix_w + r * NMAX;
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < NMAX; ++j) acc = row_acc(acc, w[j], v[j]);
+    if (c < P) Y[(long)r * P + c] = (float)acc;
+  }
+}
+
+int afl_mix_rows(const float* U, const double* W, int N, int R, long P, float* Y, hipStream_t s) {
+  if (N < 1 || N > 64 || R < 1 || R > 64 || P < 1) return (int)hipErrorInvalidValue;
+  dim3 g(afl_cdiv(P, 256)), b(256);
+  const size_t lds = sizeof(double) * (size_t)R;  // x NMAX
+  if (N <= 8) hipLaunchKernelGGL(k_mix_rows<8>, g, b, lds * 8, s, U, W, N, R, P, Y);
+  else if (N <= 16) hipLaunchKernelGGL(k_mix_rows<16>, g, b, lds * 16, s, U, W, N, R, P, Y);
+  else if (N <= 32) hipLaunchKernelGGL(k_mix_rows<32>, g, b, lds * 32, s, U, W, N, R, P, Y);
+  else hipLaunchKernelGGL(k_mix_rows<64>, g, b, lds * 64, s, U, W, N, R, P, Y);
+  return (int)hipGetLastError();
 }
 
 // ============================================================================ pairwise sq-dist
@@ -1265,9 +1317,9 @@ constexpr int BSA_TRIED = 4, BSA_ACC = 20;  // (the st[40] layout of linalg.hip 
 // caller has synchronised after filling them): sort, score, pick.  Every trip count is fixed by (n, rounds): no
 // loop depends on a value.  -> the active mask after ``rounds`` picks (wave-uniform), ``first`` = the first pick.
 // ``sel`` / ``scores`` may be null (k_agr_bisect only wants the mask).
-__device__ __forceinline__ unsigned long long krum_select_wave(double* V, unsigned char* J, int n, int f, int rounds,
-                                                               int iterated, int* __restrict__ sel,
-                                                               double* __restrict__ scores, int& first) {
+// Lane i sorts row i of (V, J) by (value, column): a stable insertion sort in LDS, the columns being in ascending order
+// on entry (krum_select_wave, k_nnm_weights).
+__device__ __forceinline__ void sort_rows_wave(double* V, unsigned char* J, int n) {
   const int i = threadIdx.x;
   if (i < n) {
     double* v = V + i * KS_LD;
@@ -1285,6 +1337,13 @@ __device__ __forceinline__ unsigned long long krum_select_wave(double* V, unsign
       jx[q + 1] = jp;
     }
   }
+}
+
+__device__ __forceinline__ unsigned long long krum_select_wave(double* V, unsigned char* J, int n, int f, int rounds,
+                                                               int iterated, int* __restrict__ sel,
+                                                               double* __restrict__ scores, int& first) {
+  const int i = threadIdx.x;
+  sort_rows_wave(V, J, n);
   unsigned long long act = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
   double sc = 0.0;
   first = 0;
@@ -1346,6 +1405,53 @@ int afl_krum_select(const double* D, int n, int f, int rounds, int iterated, int
   if (n < 1 || n > GMM_MAXN || f < 0 || f > n || rounds < 1 || rounds > n || (iterated != 0 && iterated != 1))
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_krum_select, dim3(1), dim3(64), 0, s, D, n, f, rounds, iterated, sel, mask, scores);
+  return (int)hipGetLastError();
+}
+
+// ============================================================================ nnm_weights
+// Nearest-neighbour mixing (Allouah et al., AISTATS 2023; docs/PARITY.md): the mixing matrix W [n][n] from the squared
+// distances D [n][n] (fp64, n <= 64, read as symmetric from the upper triangle like k_krum_select).  Row i mixes itself
+// and the first k = n - f - 1 other rows by (D_ij, j) ascending, a NaN distance counting as +inf; W_ij = inv =
+// 1 / (n - f) (formed on the host in fp64) on that set N_i, 0 elsewhere; nbr[i] = N_i as a 64-bit mask.
+// One wave, lane i owns row i and sorts it with the sort of krum_select; the walk along the sorted row has a fixed trip
+// count (f = 0 is no special case).  W is written with coalesced stores from the masks in LDS.
+__global__ void __launch_bounds__(64) k_nnm_weights(const double* __restrict__ D, int n, int k, double inv,
+                                                    double* __restrict__ W, unsigned long long* __restrict__ nbr) {
+  __shared__ double V[GMM_MAXN * KS_LD];
+  __shared__ unsigned char J[GMM_MAXN * KS_LD];
+  __shared__ unsigned long long M[GMM_MAXN];
+  const int i = threadIdx.x;
+  for (int e = i; e < n * n; e += 64) {
+    const int r = e / n, c = e - r * n;
+    const double d = r <= c ? D[e] : D[c * n + r];
+    V[r * KS_LD + c] = d != d ? INFINITY : d;
+    J[r * KS_LD + c] = (unsigned char)c;
+  }
+  __syncthreads();
+  sort_rows_wave(V, J, n);
+  unsigned long long m = 0ull;
+  if (i < n) {
+    m = 1ull << i;
+    int cnt = 0;
+    for (int p = 0; p < n; ++p) {
+      const int j = J[i * KS_LD + p];
+      const bool take = j != i && cnt < k;
+      m |= take ? (1ull << j) : 0ull;
+      cnt += take ? 1 : 0;
+    }
+    M[i] = m;
+    nbr[i] = m;
+  }
+  __syncthreads();
+  for (int e = i; e < n * n; e += 64) {
+    const int r = e / n, c = e - r * n;
+    W[e] = ((M[r] >> c) & 1ull) ? inv : 0.0;
+  }
+}
+
+int afl_nnm_weights(const double* D, int n, int f, double* W, unsigned long long* nbr, hipStream_t s) {
+  if (n < 1 || n > GMM_MAXN || f < 0 || f > n - 1) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_nnm_weights, dim3(1), dim3(64), 0, s, D, n, n - f - 1, 1.0 / (double)(n - f), W, nbr);
   return (int)hipGetLastError();
 }
 
