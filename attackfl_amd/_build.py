@@ -71,32 +71,46 @@ def _compile(src: str, flags, verbose: bool) -> str:
     return obj
 
 
-def build(verbose: bool = False, jobs: int = 0) -> str:
-    inc, lib, abi = _torch_paths()
-    py_inc = sysconfig.get_paths()["include"]
-    common = ["-O3", "-fPIC", "-std=c++17", f"-D_GLIBCXX_USE_CXX11_ABI={abi}", "-D__HIP_PLATFORM_AMD__",
-              "-I" + os.path.join(ROOT, "csrc")]
-    dev_flags = common + [f"--offload-arch={ARCH}", "-ffast-math", "-fno-gpu-rdc", "-munsafe-fp-atomics"]
-    dev_flags = [f for f in dev_flags if f != "-ffast-math"]  # keep IEEE semantics (NaN checks in kernels)
-    host_flags = common + ["-DTORCH_EXTENSION_NAME=_C", "-DTORCH_API_INCLUDE_EXTENSION_H", "-DUSE_ROCM",
-                           "-I" + py_inc, "-I" + os.path.join(ROCM, "include")] + ["-I" + p for p in inc] + ["-x", "c++"]
-    kernels = sorted(glob.glob(os.path.join(ROOT, "csrc", "kernels", "*.hip")))
-    # per-file device flags: the on-chip trainers' MFMAs accumulate in VGPRs.  rnn2 keeps its optimizer state in AGPRs
-    # (otherwise the accumulators compete with that state for the AGPR half of the budget); tf2 uses no AGPRs at all
-    # (onchip.h ONCHIP_NO_AGPR), and an AGPR-form MFMA would bring the 128 + 128 split back
-    extra = {f: ["-mllvm", "-amdgpu-mfma-vgpr-form"] for f in ("tf2.hip", "tf2_stamps.hip", "rnn2.hip", "rnn2_stamps.hip")}
+def _common_flags():
+    abi = _torch_paths()[2]
+    return ["-O3", "-fPIC", "-std=c++17", f"-D_GLIBCXX_USE_CXX11_ABI={abi}", "-D__HIP_PLATFORM_AMD__",
+            "-I" + os.path.join(ROOT, "csrc")]
+
+
+# per-file device flags: the on-chip trainers' MFMAs accumulate in VGPRs.  rnn2 keeps its optimizer state in AGPRs
+# (otherwise the accumulators compete with that state for the AGPR half of the budget); tf2 uses no AGPRs at all
+# (onchip.h ONCHIP_NO_AGPR), and an AGPR-form MFMA would bring the 128 + 128 split back
+VGPR_FORM_MFMA = ("tf2.hip", "tf2_stamps.hip", "rnn2.hip", "rnn2_stamps.hip")
+# diagnostic ablation builds of the stamped trainers (tools/phase_profile.py): AFL_TF2_ABL / AFL_RNN2_ABL -> -D<name>=bits
+ABL = {"tf2_stamps.hip": "TF2_ABL", "rnn2_stamps.hip": "RNN2_ABL"}
+
+
+def device_flags(src: str) -> list:
+    """The device compile flags of one kernel file: the one statement of them (tools/isa_phase_counts.py compiles to
+    assembly with the same line)."""
+    name = os.path.basename(src)
+    # (IEEE semantics, no -ffast-math: the kernels test for NaN)
+    flags = _common_flags() + [f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-munsafe-fp-atomics"]
     if os.environ.get("AFL_DEV_DEFINES"):  # A/B variant builds (tools/ab_native.sh): extra -D flags on every kernel
-        dev_flags = dev_flags + os.environ["AFL_DEV_DEFINES"].split()
-    if os.environ.get("AFL_TF2_ABL"):  # diagnostic ablation build of the timed kernel (tools/phase_profile.py)
-        extra["tf2_stamps.hip"] = extra["tf2_stamps.hip"] + ["-DTF2_ABL=" + str(int(os.environ["AFL_TF2_ABL"]))]
-    if os.environ.get("AFL_RNN2_ABL"):  # diagnostic ablation build of the stamped RNN trainer
-        extra["rnn2_stamps.hip"] = extra["rnn2_stamps.hip"] + ["-DRNN2_ABL=" + str(int(os.environ["AFL_RNN2_ABL"]))]
-    if os.environ.get("AFL_RNN2_DEBUG"):  # diagnostic printf build of the on-chip RNN trainer
-        extra["rnn2.hip"] = extra["rnn2.hip"] + ["-DRNN2_" + os.environ["AFL_RNN2_DEBUG"]]
+        flags += os.environ["AFL_DEV_DEFINES"].split()
+    if name in VGPR_FORM_MFMA:
+        flags += ["-mllvm", "-amdgpu-mfma-vgpr-form"]
+    abl = ABL.get(name)
+    if abl and os.environ.get("AFL_" + abl):
+        flags.append(f"-D{abl}=" + str(int(os.environ["AFL_" + abl])))
+    return flags
+
+
+def build(verbose: bool = False, jobs: int = 0) -> str:
+    inc, lib, _ = _torch_paths()
+    py_inc = sysconfig.get_paths()["include"]
+    host_flags = _common_flags() + ["-DTORCH_EXTENSION_NAME=_C", "-DTORCH_API_INCLUDE_EXTENSION_H", "-DUSE_ROCM",
+                                    "-I" + py_inc, "-I" + os.path.join(ROCM, "include")] + ["-I" + p for p in inc] + ["-x", "c++"]
+    kernels = sorted(glob.glob(os.path.join(ROOT, "csrc", "kernels", "*.hip")))
     hosts = sorted(glob.glob(os.path.join(ROOT, "csrc", "*.cpp")) + glob.glob(os.path.join(ROOT, "csrc", "comm", "*.cpp")))
     jobs = jobs or min(8, int(os.environ.get("MAX_JOBS", os.cpu_count() or 4)))
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
-        futs = [ex.submit(_compile, s, dev_flags + extra.get(os.path.basename(s), []), verbose) for s in kernels]
+        futs = [ex.submit(_compile, s, device_flags(s), verbose) for s in kernels]
         futs += [ex.submit(_compile, s, host_flags, verbose) for s in hosts]
         objs = [f.result() for f in futs]
     cmd = [os.path.join(ROCM, "bin", "hipcc"), "-shared", "-fPIC", f"--offload-arch={ARCH}"] + objs + [

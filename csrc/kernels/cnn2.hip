@@ -1,6 +1,8 @@
 // CNNModel on-chip trainer: ONE launch trains every local client for its whole local round (all epochs,
-// forward, backward, Adam) — the CNN counterpart of tf2.hip / rnn2.hip.  Reference model: src/Model.py:27-88
-// (two Conv1d(1->32->64->128, k3, p1) + ReLU towers over vitals[7] / labs[16], AdaptiveAvgPool1d(4),
+// forward, backward, Adam) — the CNN counterpart of tf2.hip / rnn2.hip, built from the same device toolkit
+// (onchip.h: MFMA / bf16 packing, transposed LDS reads, guarded 16-byte write-through stores, the LDS-only
+// barrier); its own are the padded-row conv layout, the counter hand-offs and an in-kernel Adam.
+// Reference model: src/Model.py:27-88 (two Conv1d(1->32->64->128, k3, p1) + ReLU towers over vitals[7] / labs[16], AdaptiveAvgPool1d(4),
 // Dropout(0.3), fc1 1024->128 -> fc2 64 -> fc3 32 -> output 1, sigmoid-BCE); trainer semantics
 // client.py:66-112 (fresh Adam per round, size-1 batches skipped, NaN loss aborts the client).
 //
@@ -29,38 +31,33 @@
 // barrier after the partials, tower group barrier after the new images.  A client's 25 workgroups are
 // blockIdx c, c + C, c + 2C, ... (one XCD at C = 8 under round-robin placement: speed only).  Every wait
 // has a wall-clock deadline (s_memrealtime): a missing partner is an error, never a hang.
-#include "common.h"
-#include "kernels.h"
+#include "onchip.h"
 
 namespace {
 
-typedef short s8v __attribute__((ext_vector_type(8)));
-typedef short s4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf8v __attribute__((ext_vector_type(8)));
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef __bf16 b2v __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2v __attribute__((ext_vector_type(2)));
-#define LDS_AS __attribute__((address_space(3)))
-#define GAS __attribute__((address_space(1)))
-typedef GAS uint32_t gu32;
-typedef unsigned char uchar;
+// the on-chip trainers' shared toolkit (onchip.h), name by name: cnn2 keeps an Adam, an opaque phase entry and
+// hand-offs of its own under names oc:: has too (adam1, AdamK; REOPQ, arrive / wait_ge / wait_wave)
+using oc::cat44;
+using oc::ld_wt;
+using oc::lds_bar;
+using oc::ldsf;
+using oc::mma;
+using oc::NTH;  // 8 waves
+using oc::of2v;
+using oc::pk2;
+using oc::rsrc;
+using oc::st_wt;
+using oc::store_guard;
+using oc::tr16;
+using oc::u32x2v;
+using oc::u32x4;
+using oc::uchar;
+using oc::Z4;
 
-constexpr int NTH = 512;  // 8 waves
 constexpr int NWG = 32;   // workgroups per client: 8 vitals + 16 labs towers + head + 7 fc1 owners
 constexpr int WG_HEAD = 24, WG_FC1 = 25, NFC1 = 7;
 constexpr long DEADLINE = 200000000L;  // s_memrealtime ticks (100 MHz): 2 s per wait
 
-__device__ __forceinline__ f4v mfma(s8v a, s8v b, f4v c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8v, a), __builtin_bit_cast(bf8v, b), c, 0, 0, 0);
-}
-constexpr f4v Z4 = {0.f, 0.f, 0.f, 0.f};
-__device__ __forceinline__ unsigned short bfu(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }
-__device__ __forceinline__ uint32_t pk2(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f2v){a, b}, b2v));
-}
-__device__ __forceinline__ float bff(unsigned short h) { return __uint_as_float(((uint32_t)h) << 16); }
 __device__ __forceinline__ float relu(float v) { return v < 0.f ? 0.f : v; }  // keeps NaN like torch
 __host__ __device__ constexpr int bin_lo(int p, int L) { return (p * L) / 4; }
 __host__ __device__ constexpr int bin_hi(int p, int L) { return ((p + 1) * L + 3) / 4; }
@@ -75,52 +72,28 @@ __device__ __forceinline__ s8v rfrag(const uchar* S, int ld, int r0, int k0, int
 __device__ __forceinline__ s8v cfrag(const uchar* S, int ld, int k0, int m0, int lane) {
   const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
   const uchar* a1 = S + ((k0 + 8 * g + q) * ld + m0 + 4 * p) * 2;
-  const s4v r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s4v*)a1);
-  const s4v r2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s4v*)(a1 + 4 * ld * 2));
-  s8v r;
-  r[0] = r1[0]; r[1] = r1[1]; r[2] = r1[2]; r[3] = r1[3];
-  r[4] = r2[0]; r[5] = r2[1]; r[6] = r2[2]; r[7] = r2[3];
-  return r;
+  return cat44(tr16(a1), tr16(a1 + 4 * ld * 2));
 }
 __device__ __forceinline__ LDS_AS unsigned short* lu16(uchar* S, int byte_off) {
   return (LDS_AS unsigned short*)(S + byte_off);
 }
-__device__ __forceinline__ LDS_AS float* lf(uchar* S, int byte_off) { return (LDS_AS float*)(S + byte_off); }
 
 // ---- global hand-off memory: 16-byte sc1 (write-through) stores / sc1 loads through a buffer resource ----
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7fffffff, 0x00020000);
-}
-// a 16-byte vector-memory store reads its data VGPRs after issue: a VALU write to them in the next cycle can
-// land in the stored data (onchip.h store_guard); every b128 store is followed by this pinned s_nop
-__device__ __forceinline__ void sguard() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_nop 1" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void st16(__amdgpu_buffer_rsrc_t rs, int byte_off, u32x4 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(v, rs, byte_off, 0, 16);
-  sguard();
-}
 __device__ __forceinline__ void st16f(__amdgpu_buffer_rsrc_t rs, int byte_off, f4v v) {
-  st16(rs, byte_off, __builtin_bit_cast(u32x4, v));
-}
-__device__ __forceinline__ u32x4 ld16(__amdgpu_buffer_rsrc_t rs, int byte_off) {
-  return __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off, 0, 16);
+  st_wt(rs, byte_off, __builtin_bit_cast(u32x4, v));
 }
 __device__ __forceinline__ f4v ld16f(__amdgpu_buffer_rsrc_t rs, int byte_off) {
-  return __builtin_bit_cast(f4v, ld16(rs, byte_off));
+  return __builtin_bit_cast(f4v, ld_wt(rs, byte_off));
 }
 __device__ __forceinline__ s8v ld16s(__amdgpu_buffer_rsrc_t rs, int byte_off) {
-  return __builtin_bit_cast(s8v, ld16(rs, byte_off));
+  return __builtin_bit_cast(s8v, ld_wt(rs, byte_off));
 }
-// Workgroup barrier over LDS only: waits for this wave's LDS operations, not for its outstanding global loads
-// (__syncthreads() drains vmcnt too, which stalled every barrier behind the operand prefetches issued before it).
-// Global data written by the workgroup is published only through arrive(), which drains explicitly.
-__device__ __forceinline__ void lbar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // Phase entry: the lane / wave indices become opaque, so every per-lane address of a phase is computed inside
 // it (otherwise the compiler hoists the hundreds of swizzled LDS / image addresses of the step out of the loop
-// and keeps them live across all phases, spilling to scratch)
+// and keeps them live across all phases, spilling to scratch).  onchip.h's opq() with the wave index taken through
+// readfirstlane between the two opaque moves and the derived indices recomputed.
+// (kept as its own text: written as readfirstlane + oc::opq, k_cnn2_train grew 133 132 -> 133 444 bytes;
+// profiles/isa_identity_onchip_toolkit.md)
 #define REOPQ()                                   \
   do {                                            \
     __builtin_amdgcn_sched_barrier(0);            \
@@ -135,7 +108,7 @@ __device__ __forceinline__ void lbar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts
   } while (0)
 #define SYNC()        \
   do {                \
-    lbar();  \
+    lds_bar();  \
     REOPQ();          \
   } while (0)
 __device__ __forceinline__ void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
@@ -206,9 +179,9 @@ __device__ __forceinline__ bool wait_ge(const Ctx& x, int which, uint32_t target
     }
     fl[0] = ok;
   }
-  lbar();
+  lds_bar();
   const int ok = fl[0];
-  lbar();  // fl is rewritten by the next wait
+  lds_bar();  // fl is rewritten by the next wait
   return ok != 0;
 }
 
@@ -404,17 +377,17 @@ __device__ __forceinline__ void publish_conv(const Ctx& x, int i, const TowerSta
       *(LDS_AS uint32_t*)(S + O_S3 + ((blk * 192 + k.j * 64 + k.ci) * 8 + (k.o0 & 7) + 2) * 2) = pk2(st.p[u][2], st.p[u][3]);
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        *lu16(S, O_S3B + (((blk * 3 + k.j) * 8 + (k.o0 & 7) + e) * 64 + k.ci) * 2) = bfu(st.p[u][e]);
+        *lu16(S, O_S3B + (((blk * 3 + k.j) * 8 + (k.o0 & 7) + e) * 64 + k.ci) * 2) = fk::f2bf(st.p[u][e]);
     } else if (k.kind == 2) {
       *(LDS_AS uint32_t*)(S + O_S2 + ((k.j * 32 + k.ci) * 8 + (k.o0 & 7)) * 2) = pk2(st.p[u][0], st.p[u][1]);
       *(LDS_AS uint32_t*)(S + O_S2 + ((k.j * 32 + k.ci) * 8 + (k.o0 & 7) + 2) * 2) = pk2(st.p[u][2], st.p[u][3]);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) *lu16(S, O_S2B + ((k.j * 8 + (k.o0 & 7) + e) * 32 + k.ci) * 2) = bfu(st.p[u][e]);
+      for (int e = 0; e < 4; ++e) *lu16(S, O_S2B + ((k.j * 8 + (k.o0 & 7) + e) * 32 + k.ci) * 2) = fk::f2bf(st.p[u][e]);
     } else if (k.kind == 1) {
       st16f(x.rw, WS_SMALL + (T * NSMALL + k.s0) * 4, f4v{st.p[u][0], st.p[u][1], st.p[u][2], st.p[u][3]});
     }
   }
-  lbar();
+  lds_bar();
   constexpr int NB3 = T == 0 ? 2 : 1;
   // W3T [j][ci][o]: one 16-B piece (8 o) per (blk, j, ci); W3 [j][o][ci]: 8 pieces (64 ci) per (blk, j, o)
   for (int e = x.tid; e < NB3 * 192 * 2; e += NTH) {
@@ -423,10 +396,10 @@ __device__ __forceinline__ void publish_conv(const Ctx& x, int i, const TowerSta
     if (r < 192) {
       const int j = r / 64, ci = r % 64;
       const u32x4 v = *(const LDS_AS u32x4*)(S + O_S3 + (blk * 192 + j * 64 + ci) * 16);
-      st16(x.rw, WS_IMG + (tw + IM_W3T + (j * 64 + ci) * 128 + 8 * b3) * 2, v);
+      st_wt(x.rw, WS_IMG + (tw + IM_W3T + (j * 64 + ci) * 128 + 8 * b3) * 2, v);
     } else {
       const int q = r - 192, j = q / 64, o = (q % 64) >> 3, cc = q & 7;  // 8 o x 8 pieces per j
-      st16(x.rw, WS_IMG + (tw + IM_W3 + (j * 128 + 8 * b3 + o) * 64 + 8 * cc) * 2,
+      st_wt(x.rw, WS_IMG + (tw + IM_W3 + (j * 128 + 8 * b3 + o) * 64 + 8 * cc) * 2,
            *(const LDS_AS u32x4*)(S + O_S3B + (((blk * 3 + j) * 8 + o) * 64 + 8 * cc) * 2));
     }
   }
@@ -438,10 +411,10 @@ __device__ __forceinline__ void publish_conv(const Ctx& x, int i, const TowerSta
       if (e < 3 * nci) {
         const int j = e / nci, ci = ci0 + e % nci;
         const u32x4 v = *(const LDS_AS u32x4*)(S + O_S2 + (j * 32 + ci) * 16);
-        st16(x.rw, WS_IMG + (tw + IM_W2T + (j * 32 + ci) * 64 + 8 * b2) * 2, v);
+        st_wt(x.rw, WS_IMG + (tw + IM_W2T + (j * 32 + ci) * 64 + 8 * b2) * 2, v);
       } else {
         const int q = e - 3 * nci, j = q / (8 * npc), o = (q % (8 * npc)) / npc, cc = ci0 / 8 + q % npc;
-        st16(x.rw, WS_IMG + (tw + IM_W2 + (j * 64 + 8 * b2 + o) * 32 + 8 * cc) * 2,
+        st_wt(x.rw, WS_IMG + (tw + IM_W2 + (j * 64 + 8 * b2 + o) * 32 + 8 * cc) * 2,
              *(const LDS_AS u32x4*)(S + O_S2B + ((j * 8 + o) * 32 + 8 * cc) * 2));
       }
     }
@@ -471,10 +444,10 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
     }
     mv_st(x, u, Z4, Z4);
   }
-  lbar();
+  lds_bar();
   publish_conv<T>(x, i, st);
   arrive(x, CT_W + T);
-  lbar();
+  lds_bar();
   // re-zero the staging the publishers used (rows 0.. of H1 / H2 / H3)
   for (int e = tid; e < O_XS / 16; e += NTH) *(LDS_AS u32x4*)(S + 16 * e) = u32x4{0u, 0u, 0u, 0u};
 
@@ -547,7 +520,7 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
       const int n16 = buf == 0 ? LD1 / 8 : buf == 2 ? LD3 / 8 : LD2 / 8;
       for (int k = 0; k < n16; ++k) *(LDS_AS u32x4*)(S + off + 16 * k) = u32x4{0u, 0u, 0u, 0u};
     }
-    if (xq >= 0) *lf(S, O_XS + (xq + 1) * 4) = xv;
+    if (xq >= 0) *ldsf(S, O_XS + (xq + 1) * 4) = xv;
     SYNC();
     // conv1 (1 -> 32) on VALU -> H1 (bf16), pads exact zeros
 #pragma unroll
@@ -555,10 +528,10 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
       const int q = (tid >> 5) + 16 * u;
       float h = 0.f;
       if (valid_q(q, C::LP)) {
-        const float xm = *lf(S, O_XS + q * 4), x0 = *lf(S, O_XS + (q + 1) * 4), xp = *lf(S, O_XS + (q + 2) * 4);
+        const float xm = *ldsf(S, O_XS + q * 4), x0 = *ldsf(S, O_XS + (q + 1) * 4), xp = *ldsf(S, O_XS + (q + 2) * 4);
         h = relu(bb1 + w10 * xm + w11 * x0 + w12 * xp);
       }
-      *lu16(S, O_H1 + ((q + 1) * LD1 + o1) * 2) = bfu(h);
+      *lu16(S, O_H1 + ((q + 1) * LD1 + o1) * 2) = fk::f2bf(h);
     }
     SYNC();
 #ifndef CNN2_DIAG2
@@ -572,7 +545,7 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
 #pragma unroll
       for (int j = 0; j < 3; ++j)
 #pragma unroll
-        for (int t = 0; t < 2; ++t) acc[t] = mfma(w2f[j], rfrag(S + O_H1, LD1, 16 * (mt0 + 2 * t) + j, 0, lane), acc[t]);
+        for (int t = 0; t < 2; ++t) acc[t] = mma(w2f[j], rfrag(S + O_H1, LD1, 16 * (mt0 + 2 * t) + j, 0, lane), acc[t]);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int q = 16 * (mt0 + 2 * t) + li;
@@ -600,7 +573,7 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
       for (int k = 0; k < 6; ++k)
 #pragma unroll
         for (int t = 0; t < 3; ++t)
-          acc[t] = mfma(w3f[k], rfrag(S + O_H2, LD2, 16 * (mt0 + t) + (k >> 1), 32 * (k & 1), lane), acc[t]);
+          acc[t] = mma(w3f[k], rfrag(S + O_H2, LD2, 16 * (mt0 + t) + (k >> 1), 32 * (k & 1), lane), acc[t]);
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
         const int q = 16 * (mt0 + t) + li;
@@ -646,7 +619,7 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
       }
       const u32x4 pkd = u32x4{pk2(f[0], f[1]), pk2(f[2], f[3]), pk2(f[4], f[5]), pk2(f[6], f[7])};
       *(LDS_AS u32x4*)(S + O_FT + (r * LDF + 8 * cp) * 2) = pkd;
-      if (r < C::R) st16(x.rw, WS_FEAT + par * FEAT_PAR + ((b0 + r) * 1024 + C::COL0 + 8 * cp) * 2, pkd);
+      if (r < C::R) st_wt(x.rw, WS_FEAT + par * FEAT_PAR + ((b0 + r) * 1024 + C::COL0 + 8 * cp) * 2, pkd);
     }
     SYNC();
     stamp(x, kact, 9);
@@ -654,9 +627,9 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
     {
       f4v acc = Z4;
 #pragma unroll
-      for (int k = 0; k < 16; ++k) acc = mfma(rfrag(S + O_FT, LDF, 0, 32 * k, lane), wf1[k], acc);
+      for (int k = 0; k < 16; ++k) acc = mma(rfrag(S + O_FT, LDF, 0, 32 * k, lane), wf1[k], acc);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) *lf(S, O_ZS + ((4 * g + e) * LDZ + 16 * wave + li) * 4) = acc[e];
+      for (int e = 0; e < 4; ++e) *ldsf(S, O_ZS + ((4 * g + e) * LDZ + 16 * wave + li) * 4) = acc[e];
     }
     SYNC();
     for (int e = tid; e < C::R * 32; e += NTH) {
@@ -696,7 +669,7 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
     REOPQ();
     stamp(x, kact, 2);
     {
-      const u32x4 stt = ld16(x.rw, WS_STAT + 16 * hw);
+      const u32x4 stt = ld_wt(x.rw, WS_STAT + 16 * hw);
       if (stt[0] != 0u) {  // NaN loss: the client's round ends here without an update (the head saw it too)
         alive = false;
         break;
@@ -706,7 +679,7 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
     if (tid < 16 * 16) {
       const int r = tid >> 4, pc = tid & 15;
       u32x4 v = u32x4{0u, 0u, 0u, 0u};
-      if (r < C::R) v = ld16(x.rw, WS_D1 + ((b0 + r) * 128 + 8 * pc) * 2);
+      if (r < C::R) v = ld_wt(x.rw, WS_D1 + ((b0 + r) * 128 + 8 * pc) * 2);
       *(LDS_AS u32x4*)(S + O_D1R + (r * LDD + 8 * pc) * 2) = v;
     }
     SYNC();
@@ -717,12 +690,12 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
       for (int k = 0; k < 4; ++k) {
         const s8v af = rfrag(S + O_D1R, LDD, 0, 32 * k, lane);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = mfma(af, wt1[4 * t + k], acc[t]);
+        for (int t = 0; t < 4; ++t) acc[t] = mma(af, wt1[4 * t + k], acc[t]);
       }
 #pragma unroll
       for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) *lf(S, O_FT + ((4 * g + e) * 516 + 16 * (4 * wave + t) + li) * 4) = acc[t][e];
+        for (int e = 0; e < 4; ++e) *ldsf(S, O_FT + ((4 * g + e) * 516 + 16 * (4 * wave + t) + li) * 4) = acc[t][e];
     }
     SYNC();
     stamp(x, kact, 10);
@@ -764,7 +737,7 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
         b1s += v1;
       }
     }
-    *(LDS_AS f2v*)(S + O_RED + (R_DB3 + (tid >> 6) * 128 + 2 * cp) * 4) = f2v{b0s, b1s};
+    *(LDS_AS of2v*)(S + O_RED + (R_DB3 + (tid >> 6) * 128 + 2 * cp) * 4) = of2v{b0s, b1s};
     SYNC();
     stamp(x, kact, 11);
     // dh2 = relu'(h2) * sum_j shift_{1-j}(dh3) . W3_j  (K = 3 x 128): wave n-tile nb2, m-tiles mpb, mpb + 2, ..
@@ -777,7 +750,7 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
         for (int k = 0; k < 12; ++k)
 #pragma unroll
           for (int t = 0; t < 2; ++t)
-            acc[t] = mfma(w3t[k], rfrag(S + O_H3, LD3, 16 * (mt0 + 2 * t) + 2 - (k >> 2), 32 * (k & 3), lane), acc[t]);
+            acc[t] = mma(w3t[k], rfrag(S + O_H3, LD3, 16 * (mt0 + 2 * t) + 2 - (k >> 2), 32 * (k & 3), lane), acc[t]);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           if (mt0 + 2 * t >= 9) continue;
@@ -809,7 +782,7 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
       for (int k = 0; k < 6; ++k)
 #pragma unroll
         for (int t = 0; t < 3; ++t)
-          accs[t] = mfma(w2t[k], rfrag(S + O_DH2, LD2, 16 * (mpa + 4 * t) + 2 - (k >> 1), 32 * (k & 1), lane), accs[t]);
+          accs[t] = mma(w2t[k], rfrag(S + O_DH2, LD2, 16 * (mpa + 4 * t) + 2 - (k >> 1), 32 * (k & 1), lane), accs[t]);
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
         const int mt = mpa + 4 * t;
@@ -817,7 +790,7 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
         const f4v acc = accs[t];
         const int q = 16 * mt + li;
         const u32x2v hw = *(const LDS_AS u32x2v*)(S + O_H1 + ((q + 1) * LD1 + 16 * nb1 + 4 * g) * 2);
-        const float xm = *lf(S, O_XS + q * 4), x0 = *lf(S, O_XS + (q + 1) * 4), xp = *lf(S, O_XS + (q + 2) * 4);
+        const float xm = *ldsf(S, O_XS + q * 4), x0 = *ldsf(S, O_XS + (q + 1) * 4), xp = *ldsf(S, O_XS + (q + 2) * 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const uint32_t h = hw[e >> 1];
@@ -862,8 +835,8 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
         for (int t = 0; t < 6; ++t) {
           const int j = (tb + t) >> 2, ct = (tb + t) & 3;
           const s8v bf = cfrag(S + O_H2 + j * LD2 * 2, LD2, 32 * ks, 16 * ct, lane);
-          acc[0][t] = mfma(a0, bf, acc[0][t]);
-          acc[1][t] = mfma(a1, bf, acc[1][t]);
+          acc[0][t] = mma(a0, bf, acc[0][t]);
+          acc[1][t] = mma(a1, bf, acc[1][t]);
         }
       }
 #pragma unroll
@@ -884,7 +857,7 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
       for (int ks = 0; ks < 5; ++ks) {
         const s8v af = cfrag(S + O_DH2 + LD2 * 2, LD2, 32 * ks, 16 * ot, lane);
 #pragma unroll
-        for (int j = 0; j < 3; ++j) acc[j] = mfma(af, cfrag(S + O_H1 + j * LD1 * 2, LD1, 32 * ks, 16 * ct, lane), acc[j]);
+        for (int j = 0; j < 3; ++j) acc[j] = mma(af, cfrag(S + O_H1 + j * LD1 * 2, LD1, 32 * ks, 16 * ct, lane), acc[j]);
       }
 #pragma unroll
       for (int j = 0; j < 3; ++j)
@@ -898,16 +871,16 @@ __device__ __forceinline__ void tower(const Ctx& x, int i) {
       if (tid < 128) {
         const int o = tid < 96 ? tid / 3 : tid - 96, comp = tid < 96 ? tid % 3 : 3;
         const int nt = o >> 4;
-        for (int w = nt; w < 8; w += 2) v += *lf(S, O_RED + (R_C1 + (w * 16 + (o & 15)) * 4 + comp) * 4);
+        for (int w = nt; w < 8; w += 2) v += *ldsf(S, O_RED + (R_C1 + (w * 16 + (o & 15)) * 4 + comp) * 4);
       } else if (tid < 192) {
         const int o = tid - 128;
-        v = *lf(S, O_RED + (R_DB2 + (o >> 4) * 16 + (o & 15)) * 4) + *lf(S, O_RED + (R_DB2 + ((o >> 4) + 4) * 16 + (o & 15)) * 4);
+        v = *ldsf(S, O_RED + (R_DB2 + (o >> 4) * 16 + (o & 15)) * 4) + *ldsf(S, O_RED + (R_DB2 + ((o >> 4) + 4) * 16 + (o & 15)) * 4);
       } else {
         const int o = tid - 192;
 #pragma unroll
-        for (int rg = 0; rg < 8; ++rg) v += *lf(S, O_RED + (R_DB3 + 128 * rg + o) * 4);
+        for (int rg = 0; rg < 8; ++rg) v += *ldsf(S, O_RED + (R_DB3 + 128 * rg + o) * 4);
       }
-      *lf(S, O_RED + (R_SM + tid) * 4) = v;
+      *ldsf(S, O_RED + (R_SM + tid) * 4) = v;
     }
     SYNC();
     if (tid < NSMALL / 4) st16f(x.rw, pbase + (P_SM + 4 * tid) * 4, *(const LDS_AS f4v*)(S + O_RED + (R_SM + 4 * tid) * 4));
@@ -1012,16 +985,16 @@ __device__ __forceinline__ void head(const Ctx& x) {
   LDS_AS unsigned short* W2s = lu16(S, H_W2S);
   LDS_AS unsigned short* W3s = lu16(S, H_W3S);
   LDS_AS unsigned short* f2s = lu16(S, H_F2S);
-  LDS_AS float* f3f = lf(S, H_F3F);
+  LDS_AS float* f3f = ldsf(S, H_F3F);
   LDS_AS unsigned short* d3s = lu16(S, H_D3S);
   LDS_AS unsigned short* d2s = lu16(S, H_D2S);
-  LDS_AS float* dz = lf(S, H_DZ);
-  LDS_AS float* red = lf(S, H_RED);
-  LDS_AS float* wos = lf(S, H_WO);
-  LDS_AS float* red3w = lf(S, H_RED3W);
-  LDS_AS float* gbw = lf(S, H_GBW);
-  LDS_AS float* bias = lf(S, H_BIAS);
-  LDS_AS float* sums = lf(S, H_SUMS);
+  LDS_AS float* dz = ldsf(S, H_DZ);
+  LDS_AS float* red = ldsf(S, H_RED);
+  LDS_AS float* wos = ldsf(S, H_WO);
+  LDS_AS float* red3w = ldsf(S, H_RED3W);
+  LDS_AS float* gbw = ldsf(S, H_GBW);
+  LDS_AS float* bias = ldsf(S, H_BIAS);
+  LDS_AS float* sums = ldsf(S, H_SUMS);
   // persistent Adam state: dW2 elements (o = 16 (w >> 1) + 4 g + e, i = 16 (4 (w & 1) + j) + li), dW3 elements
   // (o = 16 (w >> 2) + 4 g + e, i = 16 (w & 3) + li), one vector entry per thread < 257
   float p2[16], p3[4], pv = 0.f;  // moments in slab slots 0..3 (W2), 4 (W3), 5 (vector entry)
@@ -1047,9 +1020,9 @@ __device__ __forceinline__ void head(const Ctx& x) {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) W2s[(o2b + e) * H_L1 + i2b + 16 * j] = bfu(p2[4 * j + e]);
+      for (int e = 0; e < 4; ++e) W2s[(o2b + e) * H_L1 + i2b + 16 * j] = fk::f2bf(p2[4 * j + e]);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) W3s[(o3b + e) * H_L2 + i3] = bfu(p3[e]);
+    for (int e = 0; e < 4; ++e) W3s[(o3b + e) * H_L2 + i3] = fk::f2bf(p3[e]);
     if (tid < 257) {
       if (tid < 64) bias[128 + tid] = pv;
       else if (tid < 96) bias[192 + tid - 64] = pv;
@@ -1059,7 +1032,7 @@ __device__ __forceinline__ void head(const Ctx& x) {
     }
   };
   put_state();
-  lbar();
+  lds_bar();
 
   const int min_bs = a.min_bs;
   int kact = 0;
@@ -1078,7 +1051,7 @@ __device__ __forceinline__ void head(const Ctx& x) {
     const float yv = yrow >= 0 ? a.rows[(long)yrow * 24 + 23] : 0.f;
     if (nan_seen) {  // the previous step's loss was NaN: status only, the client's round ends (towers read it)
       if (tid == 0) {
-        for (int w = 0; w < 8; ++w) st16(x.rw, WS_STAT + 16 * w, u32x4{1u, (uint32_t)s, 0u, 0u});
+        for (int w = 0; w < 8; ++w) st_wt(x.rw, WS_STAT + 16 * w, u32x4{1u, (uint32_t)s, 0u, 0u});
         a.failed[c] = 1;
       }
       arrive(x, CT_H);
@@ -1117,7 +1090,7 @@ __device__ __forceinline__ void head(const Ctx& x) {
       for (int k0 = 0; k0 < 128; k0 += 32) {
         const s8v bf = rfrag(S + H_F1S, H_L1, m0, k0, lane);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = mfma(rfrag(S + H_W2S, H_L1, 16 * j, k0, lane), bf, acc[j]);
+        for (int j = 0; j < 4; ++j) acc[j] = mma(rfrag(S + H_W2S, H_L1, 16 * j, k0, lane), bf, acc[j]);
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -1133,7 +1106,7 @@ __device__ __forceinline__ void head(const Ctx& x) {
       for (int k0 = 0; k0 < 64; k0 += 32) {
         const s8v bf = rfrag(S + H_F2S, H_L2, m0, k0, lane);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[j] = mfma(rfrag(S + H_W3S, H_L2, 16 * j, k0, lane), bf, acc[j]);
+        for (int j = 0; j < 2; ++j) acc[j] = mma(rfrag(S + H_W3S, H_L2, 16 * j, k0, lane), bf, acc[j]);
       }
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
@@ -1184,7 +1157,7 @@ __device__ __forceinline__ void head(const Ctx& x) {
       const s8v af = rfrag(S + H_D3S, H_L3, m0, 0, lane);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const f4v acc = mfma(af, cfrag(S + H_W3S, H_L2, 0, 16 * j, lane), Z4);
+        const f4v acc = mma(af, cfrag(S + H_W3S, H_L2, 0, 16 * j, lane), Z4);
         const int n = 16 * j + li;
         float cs = 0.f;
 #pragma unroll
@@ -1192,7 +1165,7 @@ __device__ __forceinline__ void head(const Ctx& x) {
           const int m = m0 + 4 * g + e;
           const unsigned short fb = f2s[m * H_L2 + n];
           const float v = (fb != 0 && !(fb & 0x8000)) ? acc[e] : 0.f;
-          d2s[m * H_L2 + n] = bfu(v);
+          d2s[m * H_L2 + n] = fk::f2bf(v);
           cs += v;
         }
         cs += __shfl_xor(cs, 16, 64);
@@ -1207,8 +1180,8 @@ __device__ __forceinline__ void head(const Ctx& x) {
       const s8v b0 = rfrag(S + H_D2S, H_L2, m0, 0, lane), b1 = rfrag(S + H_D2S, H_L2, m0, 32, lane);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        f4v acc = mfma(cfrag(S + H_W2S, H_L1, 0, 16 * j, lane), b0, Z4);
-        acc = mfma(cfrag(S + H_W2S, H_L1, 32, 16 * j, lane), b1, acc);
+        f4v acc = mma(cfrag(S + H_W2S, H_L1, 0, 16 * j, lane), b0, Z4);
+        acc = mma(cfrag(S + H_W2S, H_L1, 32, 16 * j, lane), b1, acc);
         const u32x2v fb = *(const LDS_AS u32x2v*)(f1s + row * H_L1 + 16 * j + 4 * g);
         float v[4];
 #pragma unroll
@@ -1226,7 +1199,7 @@ __device__ __forceinline__ void head(const Ctx& x) {
     for (int j = 0; j < 8; ++j) {
       __builtin_amdgcn_raw_buffer_store_b64(u32x2v{d1p[2 * j], d1p[2 * j + 1]}, x.rw,
                                             WS_D1 + (row * 128 + 16 * j + 4 * g) * 2, 0, 16);
-      sguard();
+      store_guard();
     }
     stamp(x, kact, 6);
     // per-wave hand-off with NO workgroup barrier: this wave's status slot, drained with its d1 rows, then its
@@ -1234,7 +1207,7 @@ __device__ __forceinline__ void head(const Ctx& x) {
     // (and its NaN test) is summed after the hand-off; a NaN step is caught at the next step's start, where
     // the abort goes out through the same status slots (the failed client's round is discarded either way:
     // the reference's client.py:100-102 abort, one step later on the device)
-    if (lane == 0) st16(x.rw, WS_STAT + 16 * wave, u32x4{0u, (uint32_t)s, 0u, 0u});
+    if (lane == 0) st_wt(x.rw, WS_STAT + 16 * wave, u32x4{0u, (uint32_t)s, 0u, 0u});
     drain();
     stamp(x, kact, 8);
     if (lane == 0) __hip_atomic_fetch_add(x.ctr + (CT_HW + wave) * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1252,8 +1225,8 @@ __device__ __forceinline__ void head(const Ctx& x) {
       const s8v a0 = rfrag(S + H_D2S, H_L2, m0, 0, lane), a1 = rfrag(S + H_D2S, H_L2, m0, 32, lane);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        f4v acc = mfma(a0, cfrag(S + H_W2S, H_L1, 0, 16 * j, lane), Z4);
-        acc = mfma(a1, cfrag(S + H_W2S, H_L1, 32, 16 * j, lane), acc);
+        f4v acc = mma(a0, cfrag(S + H_W2S, H_L1, 0, 16 * j, lane), Z4);
+        acc = mma(a1, cfrag(S + H_W2S, H_L1, 32, 16 * j, lane), acc);
         const int n = 16 * j + li;
         float cs = 0.f;
 #pragma unroll
@@ -1295,7 +1268,7 @@ __device__ __forceinline__ void head(const Ctx& x) {
       g3 = Z4;
 #pragma unroll
       for (int k0 = 0; k0 < 128; k0 += 32)
-        g3 = mfma(cfrag(S + H_D3S, H_L3, k0, o0, lane), cfrag(S + H_F2S, H_L2, k0, ii0, lane), g3);
+        g3 = mma(cfrag(S + H_D3S, H_L3, k0, o0, lane), cfrag(S + H_F2S, H_L2, k0, ii0, lane), g3);
     }
     SYNC();
     if (tid < 32 || tid == 64) {
@@ -1335,7 +1308,7 @@ __device__ __forceinline__ void head(const Ctx& x) {
       for (int k0 = 0; k0 < 128; k0 += 32) {
         const s8v af = cfrag(S + H_D2S, H_L2, k0, o0, lane);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) g2[j] = mfma(af, cfrag(S + H_F1S, H_L1, k0, 16 * (ib + j), lane), g2[j]);
+        for (int j = 0; j < 4; ++j) g2[j] = mma(af, cfrag(S + H_F1S, H_L1, k0, 16 * (ib + j), lane), g2[j]);
       }
     }
     // Adam on the head parameters (off the critical path: the towers run their backward meanwhile)
@@ -1403,12 +1376,12 @@ __device__ __forceinline__ void fc1_publish(const Ctx& x, int tid, int c0, int n
   for (int t = 0; t < 10; ++t)
     if (t < ntl)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) *lu16(S, F_SW + ((16 * wave + 4 * g + e) * F_LDF + 16 * t + li) * 2) = bfu(p[t][e]);
-  lbar();
+      for (int e = 0; e < 4; ++e) *lu16(S, F_SW + ((16 * wave + 4 * g + e) * F_LDF + 16 * t + li) * 2) = fk::f2bf(p[t][e]);
+  lds_bar();
   const int ncol = 16 * ntl, pr = ncol / 8;
   for (int e = tid; e < 128 * pr; e += NTH) {  // W1 [n][1024]: pr pieces of 8 columns per row
     const int n = e / pr, pc = e % pr;
-    st16(x.rw, WS_IMG + (IM_W1 + par * IM_FC1PAR + n * 1024 + c0 + 8 * pc) * 2,
+    st_wt(x.rw, WS_IMG + (IM_W1 + par * IM_FC1PAR + n * 1024 + c0 + 8 * pc) * 2,
          *(const LDS_AS u32x4*)(S + F_SW + (n * F_LDF + 8 * pc) * 2));
   }
   for (int e = tid; e < ncol * 16; e += NTH) {  // W1T [1024][n]: 16 pieces of 8 n per column
@@ -1420,7 +1393,7 @@ __device__ __forceinline__ void fc1_publish(const Ctx& x, int tid, int c0, int n
       const unsigned short hi = *lu16(S, F_SW + ((8 * pc + 2 * h + 1) * F_LDF + col) * 2);
       w[h] = (uint32_t)lo | ((uint32_t)hi << 16);
     }
-    st16(x.rw, WS_IMG + (IM_W1T + par * IM_FC1PAR + (c0 + col) * 128 + 8 * pc) * 2, u32x4{w[0], w[1], w[2], w[3]});
+    st_wt(x.rw, WS_IMG + (IM_W1T + par * IM_FC1PAR + (c0 + col) * 128 + 8 * pc) * 2, u32x4{w[0], w[1], w[2], w[3]});
   }
 }
 
@@ -1449,18 +1422,18 @@ __device__ __forceinline__ void fc1_owner(const Ctx& x, int j) {
     if (!wait_ge(x, CT_H, (uint32_t)(kact + 1), F_FLAG)) break;
     REOPQ();
     stamp(x, kact, 0);
-    if (ld16(x.rw, WS_STAT)[0] != 0u) break;  // NaN loss: the client's round ends without an update
+    if (ld_wt(x.rw, WS_STAT)[0] != 0u) break;  // NaN loss: the client's round ends without an update
     // d1 (all rows) and this block's feature columns -> LDS
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int e = tid + NTH * u, r = e >> 4, pc = e & 15;
-      *(LDS_AS u32x4*)(S + F_D1 + (r * LDD + 8 * pc) * 2) = ld16(x.rw, WS_D1 + (r * 128 + 8 * pc) * 2);
+      *(LDS_AS u32x4*)(S + F_D1 + (r * LDD + 8 * pc) * 2) = ld_wt(x.rw, WS_D1 + (r * 128 + 8 * pc) * 2);
     }
     const int pr = 2 * ntl;  // 16-B pieces per feature row
     for (int e = tid; e < 128 * pr; e += NTH) {
       const int r = e / pr, pc = e % pr;
       *(LDS_AS u32x4*)(S + F_FW + (r * F_LDF + 8 * pc) * 2) =
-          ld16(x.rw, WS_FEAT + par * FEAT_PAR + (r * 1024 + c0 + 8 * pc) * 2);
+          ld_wt(x.rw, WS_FEAT + par * FEAT_PAR + (r * 1024 + c0 + 8 * pc) * 2);
     }
     f4v m[10], v[10];  // moments in flight during the staging barrier and the MFMAs (off the critical path)
 #pragma unroll
@@ -1474,7 +1447,7 @@ __device__ __forceinline__ void fc1_owner(const Ctx& x, int j) {
       const s8v af = cfrag(S + F_D1, LDD, 32 * ks, 16 * wave, lane);
 #pragma unroll
       for (int t = 0; t < 10; ++t)
-        if (t < ntl) acc[t] = mfma(af, cfrag(S + F_FW, F_LDF, 32 * ks, 16 * t, lane), acc[t]);
+        if (t < ntl) acc[t] = mma(af, cfrag(S + F_FW, F_LDF, 32 * ks, 16 * t, lane), acc[t]);
     }
     const AdamT ak = adam_t(a.lr, kact + 1, a.opt_mode);
 #pragma unroll
@@ -1552,14 +1525,14 @@ constexpr int E_LDS = E_A3 + 16 * 36 * 4;
 static_assert(E_LDS <= 160 * 1024 && (E_FT & 15) == 0 && (E_A1 & 15) == 0, "cnn2 eval LDS");
 
 __device__ __forceinline__ s8v bf8(f4v lo, f4v hi) {
-  return s8v{(short)bfu(lo[0]), (short)bfu(lo[1]), (short)bfu(lo[2]), (short)bfu(lo[3]),
-             (short)bfu(hi[0]), (short)bfu(hi[1]), (short)bfu(hi[2]), (short)bfu(hi[3])};
+  return s8v{(short)fk::f2bf(lo[0]), (short)fk::f2bf(lo[1]), (short)fk::f2bf(lo[2]), (short)fk::f2bf(lo[3]),
+             (short)fk::f2bf(hi[0]), (short)fk::f2bf(hi[1]), (short)fk::f2bf(hi[2]), (short)fk::f2bf(hi[3])};
 }
 // 8 elements at stride 3 (a conv weight column over 8 input channels of one tap) -> bf16 fragment
 __device__ __forceinline__ s8v bf8s3(const float* p) {
   s8v r;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) r[e] = (short)bfu(p[3 * e]);
+  for (int e = 0; e < 8; ++e) r[e] = (short)fk::f2bf(p[3 * e]);
   return r;
 }
 
@@ -1578,7 +1551,7 @@ __device__ __forceinline__ void eval_tower(const float* P, const int* of, const 
       const int smp = s0 + q / C::LP, l = q % C::LP - 1;
       if (smp < n) v = rows[(long)smp * 24 + C::XOFF + l];
     }
-    *lf(S, E_XS + i * 4) = v;
+    *ldsf(S, E_XS + i * 4) = v;
   }
   const int o1 = tid & 31;
   const float w10 = cp1[3 * o1], w11 = cp1[3 * o1 + 1], w12 = cp1[3 * o1 + 2], bb1 = P[of[6 * T + 1] + o1];
@@ -1591,26 +1564,26 @@ __device__ __forceinline__ void eval_tower(const float* P, const int* of, const 
     w3f[k] = bf8s3(P + of[6 * T + 4] + ((16 * wave + li) * 64 + 32 * (k & 1) + 8 * g) * 3 + (k >> 1));
   const f4v b2v = *(const f4v*)(P + of[6 * T + 3] + 16 * nt2 + 4 * g);
   const f4v b3v = *(const f4v*)(P + of[6 * T + 5] + 16 * wave + 4 * g);
-  lbar();
+  lds_bar();
   // conv1 (1 -> 32) on VALU -> H1 (bf16), pads exact zeros
 #pragma unroll
   for (int u = 0; u < 9; ++u) {
     const int q = (tid >> 5) + 16 * u;
     float h = 0.f;
     if (valid_q(q, C::LP)) {
-      const float xm = *lf(S, E_XS + q * 4), x0 = *lf(S, E_XS + (q + 1) * 4), xp = *lf(S, E_XS + (q + 2) * 4);
+      const float xm = *ldsf(S, E_XS + q * 4), x0 = *ldsf(S, E_XS + (q + 1) * 4), xp = *ldsf(S, E_XS + (q + 2) * 4);
       h = relu(bb1 + w10 * xm + w11 * x0 + w12 * xp);
     }
-    *lu16(S, E_H1 + ((q + 1) * LD1 + o1) * 2) = bfu(h);
+    *lu16(S, E_H1 + ((q + 1) * LD1 + o1) * 2) = fk::f2bf(h);
   }
-  lbar();
+  lds_bar();
   // conv2 (transposed GEMM, as the trainer): wave n-tile nt2, m-tiles mp2, mp2 + 2, ...
   for (int mt0 = mp2; mt0 < 9; mt0 += 4) {
     f4v acc[2] = {Z4, Z4};
 #pragma unroll
     for (int j = 0; j < 3; ++j)
 #pragma unroll
-      for (int t = 0; t < 2; ++t) acc[t] = mfma(w2f[j], rfrag(S + E_H1, LD1, 16 * (mt0 + 2 * t) + j, 0, lane), acc[t]);
+      for (int t = 0; t < 2; ++t) acc[t] = mma(w2f[j], rfrag(S + E_H1, LD1, 16 * (mt0 + 2 * t) + j, 0, lane), acc[t]);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int q = 16 * (mt0 + 2 * t) + li;
@@ -1618,7 +1591,7 @@ __device__ __forceinline__ void eval_tower(const float* P, const int* of, const 
         *(LDS_AS u32x2v*)(S + E_H2 + ((q + 1) * LD2 + 16 * nt2 + 4 * g) * 2) = relu_pack4(acc[t], b2v, valid_q(q, C::LP));
     }
   }
-  lbar();
+  lds_bar();
   // conv3: wave = n-tile, all 9 m-tiles
 #pragma unroll
   for (int mt0 = 0; mt0 < 9; mt0 += 3) {
@@ -1627,14 +1600,14 @@ __device__ __forceinline__ void eval_tower(const float* P, const int* of, const 
     for (int k = 0; k < 6; ++k)
 #pragma unroll
       for (int t = 0; t < 3; ++t)
-        acc[t] = mfma(w3f[k], rfrag(S + E_H2, LD2, 16 * (mt0 + t) + (k >> 1), 32 * (k & 1), lane), acc[t]);
+        acc[t] = mma(w3f[k], rfrag(S + E_H2, LD2, 16 * (mt0 + t) + (k >> 1), 32 * (k & 1), lane), acc[t]);
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
       const int q = 16 * (mt0 + t) + li;
       *(LDS_AS u32x2v*)(S + E_H3 + ((q + 1) * LD3 + 16 * wave + 4 * g) * 2) = relu_pack4(acc[t], b3v, valid_q(q, C::LP));
     }
   }
-  lbar();
+  lds_bar();
   // AdaptiveAvgPool1d(4) -> feature rows (concat column COL0 + 4 channel + bin)
 #pragma unroll
   for (int it = 0; it < 16 * 64 / NTH; ++it) {
@@ -1662,7 +1635,7 @@ __device__ __forceinline__ void eval_tower(const float* P, const int* of, const 
           u32x4{pk2(f[0], f[1]), pk2(f[2], f[3]), pk2(f[4], f[5]), pk2(f[6], f[7])};
     }
   }
-  lbar();
+  lds_bar();
 }
 
 struct AflCnn2Eval {
@@ -1682,7 +1655,7 @@ __global__ void __launch_bounds__(NTH) k_cnn2_eval(AflCnn2Eval a) {
   const float* P = a.params + (long)c * a.pstride;
   // zero the activation buffers once: their boundary rows are never written (exact zeros for every pass)
   for (int e = tid; e < E_XS / 16; e += NTH) *(LDS_AS u32x4*)(S + 16 * e) = u32x4{0u, 0u, 0u, 0u};
-  lbar();
+  lds_bar();
 #if !defined(CNN2_EVAL_ABL) || !(CNN2_EVAL_ABL & 2)  // (timing ablation: no towers)
   eval_tower<0>(P, a.off, a.rows, a.n, s0, 0, S, tid, lane, wave);
   eval_tower<1>(P, a.off, a.rows, a.n, s0, 0, S, tid, lane, wave);
@@ -1705,43 +1678,43 @@ __global__ void __launch_bounds__(NTH) k_cnn2_eval(AflCnn2Eval a) {
 #endif
       }
 #pragma unroll
-      for (int k = 0; k < 8; ++k) acc = mfma(rfrag(S + E_FT, ELDF, 0, 32 * (8 * kb + k), lane), wf[k], acc);
+      for (int k = 0; k < 8; ++k) acc = mma(rfrag(S + E_FT, ELDF, 0, 32 * (8 * kb + k), lane), wf[k], acc);
     }
     const float b1 = P[a.off[13] + 16 * wave + li];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) *lu16(S, E_A1 + ((4 * g + e) * 136 + 16 * wave + li) * 2) = bfu(relu(acc[e] + b1));
+    for (int e = 0; e < 4; ++e) *lu16(S, E_A1 + ((4 * g + e) * 136 + 16 * wave + li) * 2) = fk::f2bf(relu(acc[e] + b1));
   }
-  lbar();
+  lds_bar();
   // fc2 (128 -> 64) + ReLU on MFMA (bf16 operands, as the trainer's head): waves 0-3, n-tile = wave
   if (wave < 4) {
     const float* W2 = P + a.off[14] + (16 * wave + li) * 128 + 8 * g;
     f4v acc = Z4;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      acc = mfma(rfrag(S + E_A1, 136, 0, 32 * k, lane), bf8(*(const f4v*)(W2 + 32 * k), *(const f4v*)(W2 + 32 * k + 4)), acc);
+      acc = mma(rfrag(S + E_A1, 136, 0, 32 * k, lane), bf8(*(const f4v*)(W2 + 32 * k), *(const f4v*)(W2 + 32 * k + 4)), acc);
     const float b2 = P[a.off[15] + 16 * wave + li];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) *lu16(S, E_A2 + ((4 * g + e) * 72 + 16 * wave + li) * 2) = bfu(relu(acc[e] + b2));
+    for (int e = 0; e < 4; ++e) *lu16(S, E_A2 + ((4 * g + e) * 72 + 16 * wave + li) * 2) = fk::f2bf(relu(acc[e] + b2));
   }
-  lbar();
+  lds_bar();
   // fc3 (64 -> 32) + ReLU on MFMA: waves 0-1
   if (wave < 2) {
     const float* W3 = P + a.off[16] + (16 * wave + li) * 64 + 8 * g;
     f4v acc = Z4;
 #pragma unroll
     for (int k = 0; k < 2; ++k)
-      acc = mfma(rfrag(S + E_A2, 72, 0, 32 * k, lane), bf8(*(const f4v*)(W3 + 32 * k), *(const f4v*)(W3 + 32 * k + 4)), acc);
+      acc = mma(rfrag(S + E_A2, 72, 0, 32 * k, lane), bf8(*(const f4v*)(W3 + 32 * k), *(const f4v*)(W3 + 32 * k + 4)), acc);
     const float b3 = P[a.off[17] + 16 * wave + li];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) *lf(S, E_A3 + ((4 * g + e) * 36 + 16 * wave + li) * 4) = relu(acc[e] + b3);
+    for (int e = 0; e < 4; ++e) *ldsf(S, E_A3 + ((4 * g + e) * 36 + 16 * wave + li) * 4) = relu(acc[e] + b3);
   }
-  lbar();
+  lds_bar();
   // output (32 -> 1) + sigmoid: wave 0, lane (sample lane >> 2, quarter lane & 3)
   if (wave == 0) {
     const int r = lane >> 2, qt = lane & 3;
     float sv = 0.f;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) sv += *lf(S, E_A3 + (r * 36 + 8 * qt + k) * 4) * P[a.off[18] + 8 * qt + k];
+    for (int k = 0; k < 8; ++k) sv += *ldsf(S, E_A3 + (r * 36 + 8 * qt + k) * 4) * P[a.off[18] + 8 * qt + k];
     sv += __shfl_xor(sv, 1, 64);
     sv += __shfl_xor(sv, 2, 64);
     const float z = sv + P[a.off[19]];

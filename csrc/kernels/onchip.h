@@ -1,10 +1,25 @@
-// Shared device building blocks of the on-chip fused trainers (tf2.hip: TransformerModel, rnn2.hip:
-// RNNModel).  Both keep a client's whole model on chip for a round: fp32 master weights in AGPRs (ar / aw),
-// Adam moments in a per-workgroup global slab (mom_ld / mom_st), bf16 weight images in LDS read as MFMA A
-// operands (wfrag forward, wtfrag transposed for d(input)), activations chained in registers in the
-// "T layout" (lane (b, g) of wave w holds features 16t + 4g + i of batch row 16w + b), dW operands in
-// XOR-swizzled LDS tiles read with ds_read_b64_tr_b16 (tfrag), per-wave cross-workgroup hand-offs through
-// write-through buffer stores and flag words (publish / await).  See tf2.hip's header for the design.
+// The device toolkit of the three on-chip (persistent) trainers: tf2.hip (TransformerModel), rnn2.hip (RNNModel)
+// and cnn2.hip (CNNModel).  A helper that more than one of them needs is stated here once.
+//
+// All three use: the vector typedefs and address-space pointers (with fused_common.h), bf16 packing (pk2), the
+// 16x16x32 MFMA (mma, Z4), transposed LDS reads (tr16, cat44), buffer resources (rsrc), 16-byte write-through
+// stores / sc1 loads (st_wt / ld_wt) with the b128 store hazard guard (store_guard: stated HERE ONLY — every b128
+// store helper ends with it), the LDS-only barrier (lds_bar) and the opaque phase entry (opq).
+//
+// tf2 and rnn2 keep a client's whole model on chip for a round and share the rest: fp32 master weights parked in
+// registers behind ar / aw (rnn2: the AGPR class; tf2 defines ONCHIP_NO_AGPR and has ONE register class, 256 VGPRs
+// and no AGPRs), Adam moments in a per-workgroup global slab (mom_ld / mom_st, slot_ld / slot_st), bf16 weight
+// images in LDS read as MFMA A operands (wfrag forward, wtfrag transposed for d(input)), activations chained in
+// registers in the "T layout" (lane (b, g) of wave w holds features 16t + 4g + i of batch row 16w + b), dW
+// operands in XOR-swizzled LDS tiles read with ds_read_b64_tr_b16 (tfrag), exact cross-wave column sums (lds_addq),
+// per-wave cross-workgroup hand-offs as tagged granules (gr_put / gr_get, and the scalar-offset forms gr_put_s /
+// gr_get_s) or flag words (publish / await), LDS progress counters, wave priorities (prio_hi / prio_lo), the batch
+// walk, and the per-phase timer of the stamped builds (StampOn / StampOff).  See tf2.hip's header for the design.
+//
+// What stays in the kernel files: their LDS and workspace maps, the model-specific phases, and in cnn2.hip the
+// padded-row conv fragments (rfrag / cfrag), the counter hand-offs with a wall-clock deadline (arrive / wait_ge /
+// wait_wave), its phase entry REOPQ and its in-kernel Adam (adam1 / adam_t: bias corrections computed on the device,
+// not read from the host table adam_k uses).
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -181,14 +196,11 @@ __device__ __forceinline__ void vec8(float (&x)[8], const uchar* vec, int g) {  
 // Cost: rint + scale + convert + one select in front of the same ds_add_f64, straight-line (an int64 form with
 // the conversion done in fp32 / int32 pieces lengthened each call's dependent chain by ~150 cycles: +0.4 us per
 // TransformerModel step, measured; a poison flag through a uniform-address LDS atomic became a 64-iteration
-// scalar loop).
+// scalar loop).  Against the unquantised fp64 atomics it replaced: -0.2 % TransformerModel, -0.7 % RNNModel rounds/s
+// (profiles/ab_r5_fixed_point.md).
 constexpr float FX_SCALE = 17179869184.0f;  // 2^34
 constexpr float FX_SAT = 1125899839733760.0f;  // 2^50 - 2^26: the largest fp32 below 2^50 quanta (8 of them < 2^53)
 __device__ __forceinline__ void lds_addq(uchar* base, int idx, float v) {
-#ifdef ONCHIP_FP64_COLSUM  // A/B variant (tools/ab_native.sh): the round-4 unquantised fp64 atomics
-  __hip_atomic_fetch_add((LDS_AS double*)base + idx, (double)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  return;
-#endif
   const float av = fabsf(v);
   float x = av < 65536.f ? __builtin_rintf(v * FX_SCALE)
           : av <= 3.402823466e38f ? __builtin_copysignf(FX_SAT, v) : __builtin_nanf("");
@@ -197,9 +209,6 @@ __device__ __forceinline__ void lds_addq(uchar* base, int idx, float v) {
 }
 // the accumulated value of slot idx (read after the barrier that follows every add)
 __device__ __forceinline__ float lds_getq(const uchar* base, int idx) {
-#ifdef ONCHIP_FP64_COLSUM
-  return (float)((const LDS_AS double*)base)[idx];
-#endif
   return (float)(((const LDS_AS double*)base)[idx] * (1.0 / 17179869184.0));
 }
 // partner lane's value (bound_ctrl: 0 for a missing source, which none of these patterns has) in the
@@ -504,8 +513,8 @@ __device__ __forceinline__ void tile_adam_pair(TS& s0, TS& s1, f4v& m0, f4v& v0,
   *(LDS_AS u32x2v*)(smem + M.img + n * M.ld + pcol(16 * T1 + g4) * 2) = u32x2v{pk2(p[4], p[5]), pk2(p[6], p[7])};
 }
 
-// Adam on N independent entries in the same stages as tile_adam_pair (AGPR weights pa[], moments in place,
-// gradients g[]); returns the new weights in pn[]
+// Adam on N independent entries in the same stages as tile_adam_pair (parked weights pa[] behind ar / aw, moments
+// in place, gradients g[]); returns the new weights in pn[]
 template <int N>
 __device__ __forceinline__ void adam_staged(VS (&pa)[N], float (&m)[N], float (&v)[N], const float (&g)[N],
                                             float (&pn)[N], const AdamK& K) {
@@ -565,7 +574,8 @@ constexpr int XF_VIT = 0, XF_LAB = 1, XF_BVIT = 2, XF_BLAB = 3, XF_TMO = 4 * 8 *
 // stores per lane, each carrying two granules (each 8-byte half lands untorn).  No drain, no flag store: the
 // producer wave moves on at once, and the consumer's ONE sc1 sweep both detects and fetches the data (the
 // flag form costs a drain on the producer plus a second dependent round trip on the consumer:
-// MI355X_MICROARCH price list, handoff-1to1 vs handoff-flag).  Tags count steps within the launch (never 0),
+// MI355X_MICROARCH price list, handoff-1to1 vs handoff-flag; the flag form on these slots measured 97.4 against
+// 102.4 rounds/s, profiles/ab_tf2_r3_granule_vs_flag.log).  Tags count steps within the launch (never 0),
 // and the slots live in the per-call zeroed sync block, so a previous launch's granules never match.
 // Slot (dir, src, wave): 4 KB = [k 0..3][lane] x 16 B — one store instruction writes 1 KB contiguously.
 constexpr int GR_DIR_BYTES = 2 * 8 * 4096;
@@ -573,49 +583,6 @@ __device__ __forceinline__ int gr_off(int dir, int src, int wave, int lane) {
   return dir * GR_DIR_BYTES + (src * 8 + wave) * 4096 + lane * 16;
 }
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t gr_rsrc(gu32* sync) { return rsrc((void*)(sync + AFL_TF_SYNC_WORDS)); }
-#ifdef ONCHIP_R1_HANDOFF
-// A/B variant (tools/ab_native.sh): the flag form (R1) on the same slots — 32 B of write-through payload per
-// lane at the slot's start, the storing wave drains, lane 0 stores the tag into the slot's flag line
-// (+2048); the consumer polls the flag(s), then issues its payload loads.
-__device__ __forceinline__ void gr_put(__amdgpu_buffer_rsrc_t rg, int off, const u32x4 (&u)[2], uint32_t tag) {
-  const int lane = threadIdx.x & 63, base = off - lane * 16;
-  __builtin_amdgcn_raw_buffer_store_b128(u[0], rg, base + lane * 32, 0, 16);
-  store_guard();
-  __builtin_amdgcn_raw_buffer_store_b128(u[1], rg, base + lane * 32 + 16, 0, 16);
-  store_guard();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (lane == 0) __builtin_amdgcn_raw_buffer_store_b32(tag, rg, base + 2048, 0, 16);
-}
-template <int S>
-__device__ __forceinline__ uint32_t gr_get(__amdgpu_buffer_rsrc_t rg, const int (&off)[S], u32x4 (&out)[2 * S],
-                                           uint32_t want, int shift, gu32* tmo, int lane) {
-  uint32_t v = 0;
-  for (long spins = 0;; ++spins) {
-    bool ok = true;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const uint32_t f = __builtin_amdgcn_readfirstlane(
-          __builtin_amdgcn_raw_buffer_load_b32(rg, off[s] - lane * 16 + 2048, 0, 16));
-      if (s == 0) v = f;
-      ok = ok && (f >> shift) == want;
-    }
-    if (ok) break;
-    if (spins > fk::XWG_MAX_SPINS) {
-      if (lane == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return 0xFFFFFFFFu;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // payload loads stay below the poll
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    const int base = off[s] - lane * 16;
-    out[2 * s] = __builtin_amdgcn_raw_buffer_load_b128(rg, base + lane * 32, 0, 16);
-    out[2 * s + 1] = __builtin_amdgcn_raw_buffer_load_b128(rg, base + lane * 32 + 16, 0, 16);
-  }
-  return v;
-}
-#else
 __device__ __forceinline__ void gr_put(__amdgpu_buffer_rsrc_t rg, int off, const u32x4 (&u)[2], uint32_t tag) {
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -653,7 +620,51 @@ __device__ __forceinline__ uint32_t gr_get(__amdgpu_buffer_rsrc_t rg, const int 
     __builtin_amdgcn_s_sleep(1);
   }
 }
-#endif
+// The same hand-off with the slot's wave-uniform part of the address in the buffer instruction's SCALAR offset: the
+// per-lane part, 16 * lane + 1024 k, is the same four VGPRs for every slot, where the all-VGPR form kept one hoisted
+// address per granule store / load live across the whole step (4 + 4 per tf2 branch wave) — the values the
+// 256-register allocation spilled first.  (tf2's head and rnn2 keep the VGPR form: in the head the extra SGPRs cost a
+// second spill VGPR and sent a weight to scratch; profiles/ab_tf2_frag_pipeline.log.)
+// (gr_get and gr_get_s keep one body each: with the tag check factored into a helper both call, k_rnn2_train
+// grew 62 176 -> 62 384 bytes; profiles/isa_identity_onchip_toolkit.md)
+__device__ __forceinline__ int gr_soff(int dir, int src, int wave) { return dir * GR_DIR_BYTES + (src * 8 + wave) * 4096; }
+__device__ __forceinline__ void gr_put_s(__amdgpu_buffer_rsrc_t rg, int soff, int lane16, const u32x4 (&u)[2],
+                                         uint32_t tag) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int j = 2 * (k & 1);
+    __builtin_amdgcn_raw_buffer_store_b128(u32x4{u[k >> 1][j], tag, u[k >> 1][j + 1], tag}, rg, lane16 + k * 1024, soff, 16);
+    store_guard();
+  }
+}
+template <int S>
+__device__ __forceinline__ uint32_t gr_get_s(__amdgpu_buffer_rsrc_t rg, const int (&soff)[S], int lane16,
+                                             u32x4 (&out)[2 * S], uint32_t want, int shift, gu32* tmo, int lane) {
+  for (long spins = 0;; ++spins) {
+    u32x4 v[4 * S];
+#pragma unroll
+    for (int s = 0; s < S; ++s)
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        v[4 * s + k] = __builtin_amdgcn_raw_buffer_load_b128(rg, lane16 + k * 1024, soff[s], 16);
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 4 * S; ++i) ok = ok && (v[i][1] >> shift) == want && (v[i][3] >> shift) == want;
+    if (__builtin_amdgcn_ballot_w64(!ok) == 0) {
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        out[2 * s] = u32x4{v[4 * s][0], v[4 * s][2], v[4 * s + 1][0], v[4 * s + 1][2]};
+        out[2 * s + 1] = u32x4{v[4 * s + 2][0], v[4 * s + 2][2], v[4 * s + 3][0], v[4 * s + 3][2]};
+      }
+      return __builtin_amdgcn_readfirstlane(v[0][1]);
+    }
+    if (spins > fk::XWG_MAX_SPINS) {
+      if (lane == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return 0xFFFFFFFFu;
+    }
+    __builtin_amdgcn_s_sleep(1);
+  }
+}
 __device__ __forceinline__ gu32* xf(gu32* base, int group, int wave) { return base + (group * 8 + wave) * 32; }
 
 __device__ __forceinline__ void unpack16(const u32x4 (&u)[2], float (&x)[16]) {
@@ -709,6 +720,56 @@ __device__ __forceinline__ bool lds_wait(const uchar* smem, int off, uint32_t ta
   asm volatile("" ::: "memory");
   return true;
 }
+
+// Wave priorities: the two waves sharing a SIMD (w and w + 4) run the same critical chain, and the
+// arbiter favours the older one, so waves 4-7 finished tf2's forward 1.35 us after waves 0-3 (per-wave
+// stamps) while waves 0-3 already hashed the NEXT step's dropout masks beside them.  Critical sections
+// (forward, backward, update; the head's forward / backward) run at priority 2, the work that only has
+// to be done before the next hand-off arrives (masks, prefetch, deferred head tiles) at 0: +1.3 %
+// TransformerModel against no priorities (profiles/ab_tf2_r3_wave_priority.log).
+__device__ __forceinline__ void prio_hi() { __builtin_amdgcn_s_setprio(2); }
+__device__ __forceinline__ void prio_lo() { __builtin_amdgcn_s_setprio(0); }
+
+// ------------------------------------------------------------------------ per-phase timers (diagnostics)
+// Built only into the stamped instantiations (tf2_stamps.hip, rnn2_stamps.hip), whose `Stamp` is StampOn<ST_OFF>:
+// s_memrealtime (100 MHz) deltas of lane 0 of ONE wave (stamps[62], default 0) of ONE workgroup (stamps[63]), summed
+// over all steps in an LDS tail of ST_N u64 at the file's ST_OFF (past its SMEM_CORE), written out at the end.
+// The production kernels' `Stamp` is StampOff: no code, no registers, no LDS tail.
+// (the previous time stamp lives in LDS slot ST_N - 1 too: a register copy raised the kernel's register
+// pressure enough to change its spills, i.e. the timings being measured)
+constexpr int ST_N = 16, ST_BYTES = ST_N * 8;
+template <int ST_OFF>
+struct StampOn {
+  bool on = false;
+  int who = 0;  // the stamping thread: lane 0 of wave stamps[62]
+  uchar* smem = nullptr;
+  __device__ __forceinline__ void operator()(int id, int tid) {
+    if (!on) return;
+    const uint64_t now = __builtin_amdgcn_s_memrealtime();
+    if (tid == who) {
+      LDS_AS uint64_t* t = (LDS_AS uint64_t*)(smem + ST_OFF);
+      t[id] += now - t[ST_N - 1];
+      t[ST_N - 1] = now;
+    }
+  }
+};
+struct StampOff {
+  __device__ __forceinline__ void operator()(int, int) {}
+};
+template <int ST_OFF>
+__device__ __forceinline__ void stamp_init(StampOn<ST_OFF>& stp, const AflTfTrainArgs& a, uchar* smem) {
+  stp.on = a.stamps && (long)blockIdx.x == (long)a.stamps[63];
+  stp.who = __builtin_amdgcn_readfirstlane(a.stamps ? 64 * (int)(a.stamps[62] & 7) : 0);  // (an SGPR, not a held VGPR)
+  stp.smem = smem;
+  if (threadIdx.x == 0) *(LDS_AS uint64_t*)(smem + ST_OFF + 8 * (ST_N - 1)) = __builtin_amdgcn_s_memrealtime();
+}
+template <int ST_OFF>
+__device__ __forceinline__ void stamp_fini(StampOn<ST_OFF>& stp, const AflTfTrainArgs& a, uchar* smem, int tid) {
+  if (stp.on && tid == 0)
+    for (int i = 0; i < ST_N - 1; ++i) a.stamps[i] = *(LDS_AS uint64_t*)(smem + ST_OFF + 8 * i);
+}
+__device__ __forceinline__ void stamp_init(StampOff&, const AflTfTrainArgs&, uchar*) {}
+__device__ __forceinline__ void stamp_fini(StampOff&, const AflTfTrainArgs&, uchar*, int) {}
 
 // --------------------------------------------------------------------------- batch walk (shared plan)
 struct Walk {

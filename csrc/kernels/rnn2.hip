@@ -48,17 +48,11 @@ constexpr float LOG2E = 1.4426950408889634f;
 // ----------------------------------------------------------------------------------- LDS maps (bytes)
 // branch workgroup
 constexpr int LDW1 = 24 * 2;                       // layer-1 image row stride: K = din <= 16 (unpermuted) + pad
-#ifndef RNN2_LDW2
-#define RNN2_LDW2 (LD64 + 16)
-#endif
-#ifndef RNN2_LDW3
-#define RNN2_LDW3 (LD64 + 16)
-#endif
 // layer-2 / 3 image row strides (bytes): rows padded by 16 elements (32 B), so the gate GEMMs' fragment reads are
 // conflict-free in gfx950 banking (wfrag ds_read_b128 4 -> 0 extra cycles per instruction, wtfrag 4 -> 2;
 // tools/dbg/lds_banks.py): RNNModel +3.45 % (profiles/ab_r5_img_pad.log).  The room comes from the fp64 column-sum
 // slots moving into the layer-1 image's row padding (dbl_slot).
-constexpr int LDW2 = RNN2_LDW2, LDW3 = RNN2_LDW3;
+constexpr int LDW2 = LD64 + 16, LDW3 = LD64 + 16;
 __host__ __device__ constexpr int ldg(int l) { return l == 2 ? LDW2 : LDW3; }
 constexpr int B_W1 = 0;                            // [192][24] layer 1 combined gate matrix
 constexpr int B_W2 = B_W1 + 192 * LDW1;            // [192][72] layer 2 (K permuted, pcol)
@@ -83,12 +77,9 @@ __device__ __forceinline__ uchar* dbl_slot(uchar* smem, int idx) { return smem +
 enum { VL_LNW = 1152, VL_LNB = 1216 };
 
 // head workgroup
-#ifndef RNN2_HPAD
-#define RNN2_HPAD 0
-#endif
-// head image row strides (bytes): RNN2_HPAD=16 (32-byte padding, as tf2's head) measured neutral here (+0.07 %,
-// profiles/ab_r5_img_pad.log)
-constexpr int HLD1 = LD128 + RNN2_HPAD, HLD2 = LD32 + RNN2_HPAD;
+// head image row strides (bytes): 32-byte padding (as tf2's head) measured neutral here (+0.07 %,
+// profiles/ab_r5_img_pad.log), so the rows keep onchip.h's 8-element padding
+constexpr int HLD1 = LD128, HLD2 = LD32;
 constexpr int H_IMG_W1 = 0;                        // [32][128] fc1
 constexpr int H_IMG_W2 = H_IMG_W1 + 32 * HLD1;     // [16][32]  fc2
 constexpr int H_CAT = H_IMG_W2 + 16 * HLD2;        // tile128: cat(vitals, labs)     (X of dW1)
@@ -103,10 +94,13 @@ constexpr int H_TOTAL = H_LOSS + 64;
 enum { HV_B1 = 0, HV_B2 = 32, HV_WO = 48, HV_BO = 64, HV_N = 65 };
 
 constexpr int SMEM_CORE = B_TOTAL > H_TOTAL ? B_TOTAL : H_TOTAL;
+// the stamped instantiation (rnn2_stamps.hip) times its phases into an LDS tail (onchip.h StampOn); the production
+// kernel gets the empty Stamp
 #ifdef RNN2_STAMPS
-constexpr int ST_OFF = SMEM_CORE, ST_N = 16;       // u64 [16] per-phase timers of the stamped workgroup
-constexpr int SMEM = ST_OFF + ST_N * 8;
+using Stamp = StampOn<SMEM_CORE>;
+constexpr int SMEM = SMEM_CORE + ST_BYTES;
 #else
+using Stamp = StampOff;
 constexpr int SMEM = SMEM_CORE;
 #endif
 static_assert(SMEM <= 160 * 1024, "LDS budget");
@@ -123,53 +117,6 @@ constexpr long MOM_WG_BYTES = (long)MOM_SLOTS * NTH * 16;
 constexpr long WS_SAV = WS_MOM + 3 * MOM_WG_BYTES;
 constexpr long SAV_BR_BYTES = 2L * 8 * NTH * 16;
 constexpr long WS_BYTES = WS_SAV + 2 * SAV_BR_BYTES;
-
-// ------------------------------------------------------------------------ per-phase timers (diagnostics)
-#ifdef RNN2_STAMPS
-struct Stamp {
-  bool on = false;
-  int who = 0;  // the stamping thread: lane 0 of wave stamps[62]
-  uchar* smem = nullptr;
-  __device__ __forceinline__ void operator()(int id, int tid) {
-    if (!on) return;
-    const uint64_t now = __builtin_amdgcn_s_memrealtime();
-    if (tid == who) {
-      LDS_AS uint64_t* t = (LDS_AS uint64_t*)(smem + ST_OFF);
-      t[id] += now - t[ST_N - 1];
-      t[ST_N - 1] = now;
-    }
-  }
-};
-#else
-struct Stamp {
-  __device__ __forceinline__ void operator()(int, int) {}
-};
-#endif
-// Wave priorities (as in tf2.hip): the critical chain at 2, the work that only has to finish before the next
-// hand-off arrives (prefetch, masks, the head's deferred tiles) at 0.
-#ifndef RNN2_NO_PRIO
-__device__ __forceinline__ void prio_hi() { __builtin_amdgcn_s_setprio(2); }
-__device__ __forceinline__ void prio_lo() { __builtin_amdgcn_s_setprio(0); }
-#else
-__device__ __forceinline__ void prio_hi() {}
-__device__ __forceinline__ void prio_lo() {}
-#endif
-__device__ __forceinline__ void stamp_init(Stamp& stp, const AflTfTrainArgs& a, uchar* smem) {
-#ifdef RNN2_STAMPS
-  stp.on = a.stamps && (long)blockIdx.x == (long)a.stamps[63];
-  stp.who = a.stamps ? 64 * (int)(a.stamps[62] & 7) : 0;
-  stp.smem = smem;
-  if (threadIdx.x == 0) *(LDS_AS uint64_t*)(smem + ST_OFF + 8 * (ST_N - 1)) = __builtin_amdgcn_s_memrealtime();
-#endif
-  (void)stp; (void)a; (void)smem;
-}
-__device__ __forceinline__ void stamp_fini(Stamp& stp, const AflTfTrainArgs& a, uchar* smem, int tid) {
-#ifdef RNN2_STAMPS
-  if (stp.on && tid == 0)
-    for (int i = 0; i < ST_N - 1; ++i) a.stamps[i] = *(LDS_AS uint64_t*)(smem + ST_OFF + 8 * i);
-#endif
-  (void)stp; (void)a; (void)smem; (void)tid;
-}
 
 // Ablation switches of the diagnostic build (compile-time RNN2_ABL bits in the stamped build only, set through
 // AFL_RNN2_ABL): skip one piece of work per step to price it (numerics are wrong then; timing only).
@@ -1139,24 +1086,8 @@ __device__ __forceinline__ void head_main(const AflTfTrainArgs& a, int cid, ucha
         // fc2 tile (k tile wave & 1): every wave computes one (no branch among the MFMAs), waves 0, 1 own them
         a2 = mma(tfrag<TK32>(smem + H_A1, 32 * s, wave & 1, lane), tfrag<TK16>(smem + H_DZ2, 32 * s, 0, lane), a2);
       }
-#ifdef RNN2_TRAP
-      const f4v acc0 = acc[0], m0 = hm[0], v0 = hv[0];
-      const float p0 = ar(st.w1[0].p[0]);
-#endif
 #pragma unroll
       for (int b = 0; b < 2; ++b) tile_adam(st.w1[b], hm[b], hv[b], HW1, wave, b, lane, acc[b], K, smem);
-#ifdef RNN2_TRAP
-      if (a.stamps && !__builtin_isfinite(ar(st.w1[0].p[0]))) {
-        if (atomicCAS((unsigned long long*)a.stamps, 0ull, 1ull) == 0ull) {
-          float* d = (float*)(a.stamps + 1);
-          d[0] = cid; d[1] = step; d[2] = wave; d[3] = lane;
-          d[4] = acc0[0]; d[5] = acc0[1]; d[6] = acc0[2]; d[7] = acc0[3];
-          d[8] = m0[0]; d[9] = v0[0]; d[10] = p0; d[11] = hm[0][0]; d[12] = hv[0][0];
-          d[13] = K.lr_bc1; d[14] = K.rsqrt_bc2; d[15] = K.keep; d[16] = K.c1; d[17] = K.eps;
-        }
-      }
-#endif
-
       if (wave < 2) tile_adam(st.w2, hm[2], hv[2], HW2, wave, 0, lane, a2, K, smem);
       if (tid < HV_N) {  // the 8 waves' partial sums in a fixed order (bit-reproducible)
         const LDS_AS float* c = ldsf(smem, H_PART) + tid;
@@ -1342,9 +1273,7 @@ int afl_rnn2_train_stamped(const AflTfTrainArgs* a, hipStream_t s) {
 long afl_rnn2_ws_floats() { return r2::WS_BYTES / 4; }
 
 int afl_rnn2_train(const AflTfTrainArgs* a, hipStream_t s) {
-#ifndef RNN2_TRAP
   if (a->stamps) return afl_rnn2_train_stamped(a, s);
-#endif
 #endif
   if (const int rc = afl_launch_preamble(a, 2, 128, true, true, (const void*)K_RNN2, r2::SMEM, 3)) return rc;
   hipLaunchKernelGGL(K_RNN2, dim3(3 * a->C), dim3(oc::NTH), r2::SMEM, s, *a);

@@ -86,16 +86,10 @@ enum { VS_DB = 0, VS_VB, VS_OB, VS_G1, VS_B1, VS_F2B, VS_G2, VS_B2, VS_G3, VS_B3
 constexpr int VS_F1B = 640;  // ffn.0 bias (6 real)
 
 // head workgroup
-#ifndef TF2_HLD1
-#define TF2_HLD1 (LD128 + 16)
-#endif
-#ifndef TF2_HLD2
-#define TF2_HLD2 (LD64 + 16)
-#endif
 // head image row strides (bytes): rows padded by 16 elements (32 B), so the fragment reads are conflict-free in
 // gfx950 banking (wfrag ds_read_b128 4 -> 0 extra cycles, wtfrag 4 / 6 -> 2; tools/dbg/lds_banks.py,
 // profiles/ab_r5_img_pad.log); the head's LDS map has the room
-constexpr int HLD1 = TF2_HLD1, HLD2 = TF2_HLD2;
+constexpr int HLD1 = LD128 + 16, HLD2 = LD64 + 16;
 constexpr int H_IMG_W1 = 0;                        // [64][128] fc1
 constexpr int H_IMG_W2 = H_IMG_W1 + 64 * HLD1;     // [32][64]  fc2
 constexpr int H_CAT = H_IMG_W2 + 32 * HLD2;        // tile128: cat(vitals, labs)     (X of dWf1)
@@ -111,10 +105,13 @@ constexpr int H_TOTAL = H_CNT + 16;
 enum { HV_B1 = 0, HV_B2 = 64, HV_WO = 96, HV_BO = 128 };
 
 constexpr int SMEM_CORE = B_TOTAL > H_TOTAL ? B_TOTAL : H_TOTAL;
+// the stamped instantiation (tf2_stamps.hip) times its phases into an LDS tail (onchip.h StampOn); the production
+// kernel gets the empty Stamp
 #ifdef TF2_STAMPS
-constexpr int ST_OFF = SMEM_CORE, ST_N = 16;       // u64 [16] per-phase timers of the stamped workgroup
-constexpr int SMEM = ST_OFF + ST_N * 8;
+using Stamp = StampOn<SMEM_CORE>;
+constexpr int SMEM = SMEM_CORE + ST_BYTES;
 #else
+using Stamp = StampOff;
 constexpr int SMEM = SMEM_CORE;
 #endif
 static_assert(SMEM <= 160 * 1024, "LDS budget");
@@ -166,34 +163,6 @@ __device__ __forceinline__ uint32_t mask16(uint32_t key, uint32_t layer, int r, 
 }
 
 
-// ------------------------------------------------------------------------ per-phase timers (diagnostics)
-// Built only into the TF2_STAMPS instantiation (tf2_stamps.hip): s_memrealtime (100 MHz) deltas of
-// lane 0 of ONE wave (stamps[62], default 0) of ONE workgroup (stamps[63]), summed over all steps in LDS,
-// written out at the end.
-// The production kernel gets the empty Stamp below (no code, no registers).
-#ifdef TF2_STAMPS
-// (the previous time stamp lives in LDS slot ST_N - 1 too: a register copy raised the kernel's register
-// pressure enough to change its spills, i.e. the timings being measured)
-struct Stamp {
-  bool on = false;
-  int who = 0;  // the stamping thread: lane 0 of wave stamps[62]
-  uchar* smem = nullptr;
-  __device__ __forceinline__ void operator()(int id, int tid) {
-    if (!on) return;
-    const uint64_t now = __builtin_amdgcn_s_memrealtime();
-    if (tid == who) {
-      LDS_AS uint64_t* t = (LDS_AS uint64_t*)(smem + ST_OFF);
-      t[id] += now - t[ST_N - 1];
-      t[ST_N - 1] = now;
-    }
-  }
-};
-#else
-struct Stamp {
-  __device__ __forceinline__ void operator()(int, int) {}
-};
-#endif
-
 // Ablation switches of the diagnostic build (compile-time TF2_ABL bits, set through the AFL_TF2_ABL
 // environment variable when building tf2_stamps.hip): skip one piece of work per step to price it
 // (numerics are wrong then; timing only).  Always false in the production kernel.
@@ -202,65 +171,6 @@ enum { ABL_U3 = 1, ABL_UADAM = 2, ABL_UDW = 4, ABL_COLSUM = 8, ABL_HEADUPD = 16,
 #define ABL(K, b) ((TF2_ABL & (b)) != 0)
 #else
 #define ABL(K, b) false
-#endif
-
-
-
-// The granule hand-off of onchip.h (gr_put / gr_get) with the slot's wave-uniform part of the address in the buffer
-// instruction's SCALAR offset: the per-lane part, 16 * lane + 1024 k, is the same four VGPRs for every slot, where
-// the all-VGPR form kept one hoisted address per granule store / load live across the whole step (4 + 4 per branch
-// wave) — the values the 256-register allocation spilled first.  (The head keeps onchip.h's form: there the extra
-// SGPRs cost a second spill VGPR and sent a weight to scratch; profiles/ab_tf2_frag_pipeline.log.)
-__device__ __forceinline__ int gr_soff(int dir, int src, int wave) { return dir * GR_DIR_BYTES + (src * 8 + wave) * 4096; }
-__device__ __forceinline__ void gr_put_s(__amdgpu_buffer_rsrc_t rg, int soff, int lane16, const u32x4 (&u)[2],
-                                         uint32_t tag) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int j = 2 * (k & 1);
-    __builtin_amdgcn_raw_buffer_store_b128(u32x4{u[k >> 1][j], tag, u[k >> 1][j + 1], tag}, rg, lane16 + k * 1024, soff, 16);
-    store_guard();
-  }
-}
-template <int S>
-__device__ __forceinline__ uint32_t gr_get_s(__amdgpu_buffer_rsrc_t rg, const int (&soff)[S], int lane16,
-                                             u32x4 (&out)[2 * S], uint32_t want, int shift, gu32* tmo, int lane) {
-  for (long spins = 0;; ++spins) {
-    u32x4 v[4 * S];
-#pragma unroll
-    for (int s = 0; s < S; ++s)
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        v[4 * s + k] = __builtin_amdgcn_raw_buffer_load_b128(rg, lane16 + k * 1024, soff[s], 16);
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 4 * S; ++i) ok = ok && (v[i][1] >> shift) == want && (v[i][3] >> shift) == want;
-    if (__builtin_amdgcn_ballot_w64(!ok) == 0) {
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        out[2 * s] = u32x4{v[4 * s][0], v[4 * s][2], v[4 * s + 1][0], v[4 * s + 1][2]};
-        out[2 * s + 1] = u32x4{v[4 * s + 2][0], v[4 * s + 2][2], v[4 * s + 3][0], v[4 * s + 3][2]};
-      }
-      return __builtin_amdgcn_readfirstlane(v[0][1]);
-    }
-    if (spins > fk::XWG_MAX_SPINS) {
-      if (lane == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return 0xFFFFFFFFu;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
-}
-
-// Wave priorities: the two waves sharing a SIMD (w and w + 4) run the same critical chain, and the
-// arbiter favours the older one, so waves 4-7 finished the forward 1.35 us after waves 0-3 (per-wave
-// stamps) while waves 0-3 already hashed the NEXT step's dropout masks beside them.  Critical sections
-// (forward, backward, update; the head's forward / backward) run at priority 2, the work that only has
-// to be done before the next hand-off arrives (masks, prefetch, deferred head tiles) at 0.
-#ifndef TF2_NO_PRIO
-__device__ __forceinline__ void prio_hi() { __builtin_amdgcn_s_setprio(2); }
-__device__ __forceinline__ void prio_lo() { __builtin_amdgcn_s_setprio(0); }
-#else
-__device__ __forceinline__ void prio_hi() {}
-__device__ __forceinline__ void prio_lo() {}
 #endif
 
 // =============================================================================== branch workgroup
@@ -1201,23 +1111,6 @@ __device__ __forceinline__ void load_x(float (&x)[4], const AflTfTrainArgs& a, i
   }
 }
 
-__device__ __forceinline__ void stamp_init(Stamp& stp, const AflTfTrainArgs& a, uchar* smem) {
-#ifdef TF2_STAMPS
-  stp.on = a.stamps && (long)blockIdx.x == (long)a.stamps[63];
-  stp.who = __builtin_amdgcn_readfirstlane(a.stamps ? 64 * (int)(a.stamps[62] & 7) : 0);  // (an SGPR, not a held VGPR)
-  stp.smem = smem;
-  if (threadIdx.x == 0) *(LDS_AS uint64_t*)(smem + ST_OFF + 8 * (ST_N - 1)) = __builtin_amdgcn_s_memrealtime();
-#endif
-  (void)stp; (void)a; (void)smem;
-}
-__device__ __forceinline__ void stamp_fini(Stamp& stp, const AflTfTrainArgs& a, uchar* smem, int tid) {
-#ifdef TF2_STAMPS
-  if (stp.on && tid == 0)
-    for (int i = 0; i < ST_N - 1; ++i) a.stamps[i] = *(LDS_AS uint64_t*)(smem + ST_OFF + 8 * i);
-#endif
-  (void)stp; (void)a; (void)smem; (void)tid;
-}
-
 template <int BR>
 __device__ __forceinline__ void branch_main(const AflTfTrainArgs& a, int cid, uchar* smem) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4;
@@ -1258,11 +1151,7 @@ __device__ __forceinline__ void branch_main(const AflTfTrainArgs& a, int cid, uc
     u32x4 outp[2];
     prio_hi();
     asm volatile(";MARK fwd");
-#ifndef TF2_NO_FWD
     br_forward<BR>(smem, xin, aru(mka0), aru(mka1), sv, outp, lane, wave);
-#else
-    sv = Saved{}; outp[0] = u32x4{0,0,0,0}; outp[1] = outp[0];
-#endif
     asm volatile(";MARK fwd_end");
     stp(0, tid);
     gr_put_s(rg, gr_soff(0, BR, wave), 16 * lane, outp, (uint32_t)step);  // this wave's output rows -> head
@@ -1297,17 +1186,10 @@ __device__ __forceinline__ void branch_main(const AflTfTrainArgs& a, int cid, uc
     float dout[16];
     unpack16(du, dout);
     if (lane == 0) abort_w[wave] = fv & 1u;
-#ifndef TF2_NO_BWD
     asm volatile(";MARK bwd");
     br_backward<BR>(smem, dout, sv, bp, K, lane, wave);
     asm volatile(";MARK bwd_end");
     stp(3, tid);
-#else
-    for (int j = 0; j < 16; ++j) asm volatile("" :: "v"(dout[j]));
-    lds_signal(smem, B_CNT_C, lane);
-    lds_signal(smem, B_CNT_A, lane);
-    lds_signal(smem, B_CNT_B, lane);
-#endif
     asm volatile(";MARK upd");
     // (false: the head saw a NaN loss somewhere in the batch — the client's round fails and this step's update is
     // not applied — or a wave stopped making progress)
@@ -1871,10 +1753,7 @@ int afl_tf2_train(const AflTfTrainArgs* a, hipStream_t s) {
   int cus = 0;
   if (const int rc = afl_launch_preamble(a, 2, 128, true, true, (const void*)K_TF2, t2::SMEM, wgs, &cus)) return rc;
   AflTfTrainArgs b = *a;
-  b.cpad = (a->C + 7) / 8 * 8;
-#ifdef TF2_NO_PAD  // A/B variant: the unpadded role-major grid
-  b.cpad = a->C;
-#endif
+  b.cpad = (a->C + 7) / 8 * 8;  // (measured neutral against the unpadded grid: profiles/ab_tf2_r5_row_split.log)
   if (wgs * b.cpad > cus) b.cpad = a->C;
   hipLaunchKernelGGL(K_TF2, dim3(wgs * b.cpad), dim3(t2::NTH), t2::SMEM, s, b);
   return 0;

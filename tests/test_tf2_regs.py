@@ -1,7 +1,9 @@
 """Register allocation of the on-chip trainers, read from their gfx950 assembly through tools/isa_phase_counts.py
 (CPU: hipcc cross-compiles).  tf2.hip's kernels live in one register class: no AGPRs (so no v_accvgpr copies on the
 VALU-issue-bound step chain), no scratch, two waves per SIMD.  rnn2.hip keeps its AGPR-resident W_ih tiles: its figures
-are those of the commit before tf2.hip changed class."""
+are those of the commit before tf2.hip changed class.  All three trainers are built from csrc/kernels/onchip.h, so
+the allocation of every one of their kernels is pinned here: a change to the shared header that moves any of them
+shows up without a GPU."""
 import functools
 import os
 import shutil
@@ -22,6 +24,12 @@ RNN2_PARENT = {
     ("rnn2.hip", "k_rnn2_eval"): (114, 0, 0, 4),
     ("rnn2_stamps.hip", "k_rnn2_train_stamped"): (128, 128, 68, 2),
 }
+# cnn2.hip and k_tf2_train at the commit before cnn2.hip moved onto onchip.h (the same four figures)
+CNN2_PARENT = {
+    ("cnn2.hip", "k_cnn2_train"): (230, 0, 0, 2),
+    ("cnn2.hip", "k_cnn2_eval"): (172, 0, 0, 2),
+}
+TF2_PARENT_VGPRS = 256
 
 
 @functools.lru_cache(maxsize=None)
@@ -65,6 +73,21 @@ def test_rnn2_allocation_unchanged(name, kernel):
     d = _figures(name)[kernel]
     print(name, kernel, d)
     assert (d["NumVgprs"], d["NumAgprs"], d["ScratchSize"], d["Occupancy"]) == RNN2_PARENT[(name, kernel)]
+
+
+@needs_hipcc
+@pytest.mark.parametrize("name,kernel", sorted(CNN2_PARENT))
+def test_cnn2_allocation_unchanged(name, kernel):
+    d = _figures(name)[kernel]
+    print(name, kernel, d)
+    assert (d["NumVgprs"], d["NumAgprs"], d["ScratchSize"], d["Occupancy"]) == CNN2_PARENT[(name, kernel)]
+
+
+@needs_hipcc
+def test_tf2_vgpr_count_unchanged():
+    d = _figures("tf2.hip")["k_tf2_train"]
+    print("tf2.hip k_tf2_train", d)
+    assert d["NumVgprs"] == TF2_PARENT_VGPRS
 
 
 ASM = """\

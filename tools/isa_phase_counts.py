@@ -21,7 +21,10 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+sys.path.insert(0, ROOT)
+from attackfl_amd import _build  # noqa: E402
+
+HIPCC = os.path.join(_build.ROCM, "bin", "hipcc")
 CLASSES = ("valu", "pk", "trans", "agpr", "mfma", "lds", "vmem", "wait", "scalar")
 HEAD = ("VALU", "packed", "transc.", "AGPR copies", "MFMA", "LDS", "vector mem", "waits / nops", "scalar")
 TRANS = ("v_exp_", "v_log_", "v_rcp_", "v_rsq_", "v_sqrt_", "v_sin_", "v_cos_")
@@ -35,9 +38,7 @@ INFO_RE = re.compile(r"^;\s*(\w+):\s*(\d+)\s*$")
 
 def device_flags(path):
     """The device compile line of attackfl_amd/_build.py for this file (device side only, to assembly)."""
-    extra = ["-mllvm", "-amdgpu-mfma-vgpr-form"] if os.path.basename(path).startswith(("tf2", "rnn2")) else []
-    return ["-O3", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROOT, "csrc"), "--offload-arch=gfx950",
-            "-fno-gpu-rdc", "-munsafe-fp-atomics", "--cuda-device-only", "-S"] + extra
+    return _build.device_flags(path) + ["--cuda-device-only", "-S"]
 
 
 def compile_asm(path, defines=(), out=None):

@@ -42,8 +42,6 @@ def run(nd, E, lr, sgd, split=4):
         print("   worst slots:", worst[:8], flush=True)
 
 
-
-
 def nan_pattern(nd, E, lr, sgd):
     gpu = torch.device("cuda", 0)
     ds = synthetic_icu(3000, seed=3)
@@ -61,23 +59,6 @@ def nan_pattern(nd, E, lr, sgd):
         big = (a.abs() > 100).nonzero().tolist()
         if bad or big:
             print(f"  {s.name} shape={tuple(s.shape)} nonfinite={bad[:40]} big={big[:20]}", flush=True)
-
-
-def trap(nd, E, lr, sgd):
-    gpu = torch.device("cuda", 0)
-    ds = synthetic_icu(3000, seed=3)
-    lay = ParamLayout.for_model("RNNModel")
-    C = len(nd)
-    params = torch.stack([lay.flatten(build_model("RNNModel", seed=i).state_dict()) for i in range(C)])
-    plan = make_plan(len(ds), nd, E, [101 + i for i in range(C)], "cpu")
-    dev = params.clone().to(gpu)
-    st = torch.zeros(64, dtype=torch.int64, device=gpu)
-    R.train_clients_async(dev, DeviceTable(ds, gpu).rows, plan.order.to(gpu), plan.nd, E, 128, lr,
-                          [5 + i for i in range(C)], opt_mode=1 if sgd else 0, stamps=st)
-    torch.cuda.synchronize()
-    rec = st.cpu()
-    print("trap flag", int(rec[0]), "rec", rec[1:10].view(torch.float32).tolist(), flush=True)
-    print("nan count", int(torch.isnan(dev).sum()), flush=True)
 
 
 if __name__ == "__main__":
