@@ -18,6 +18,8 @@ Each rule returns ``AggResult(params [P] | None, ok, info)``.  Rows are in clien
 Beyond the reference (docs/PARITY.md): multi_krum, bulyan, dnc (assumed Byzantine count ``byz-f``), geomed (RFA) and
 cclip (centred clipping about the global model the round started from: the one rule that takes ``centre``).
 Pre-aggregation in front of a rule (engine ``pre-agg``): ``nnm`` (nearest-neighbour mixing) and ``bucketing``.
+``foolsgold`` (FoolsGold) is the one stateful rule: it takes and returns the clients' update history, so it is called by
+name (``fl/engine.py`` ``_foolsgold``) and is not an entry of AGGREGATORS, the table of stateless rules.
 FLTrust and the hypernetwork live in the engine (``fl/engine.py`` ``_fltrust``, ``fl/hyper_server.py``): they train.
 """
 from __future__ import annotations
@@ -29,7 +31,7 @@ from typing import Dict, Optional, Union
 import torch
 
 from .. import ops
-from ..config import BUCKET_SIZE, KNOB, PRE_AGG_KINDS  # (a knob's default and check: stated once, in config)
+from ..config import BUCKET_SIZE, FOOLSGOLD_KAPPA, KNOB, PRE_AGG_KINDS  # (a knob's default and check: stated once, in config)
 from ..ops.composite import gmm_filter_ref  # noqa: F401  (the kernel's host mirror: tools and tests import it here)
 
 
@@ -180,6 +182,38 @@ def cclip(U: torch.Tensor, sizes=None, centre: Optional[torch.Tensor] = None,
         c, t, clipped, _ = ops.cclip_weights(ops.gram_anchored(U, g), alpha, torch.zeros_like(alpha), iters, tau)
         out = ops.anchored_rows(U, c, g)
     return AggResult(out, True, {"weights": c, "tau": t, "clipped": clipped, "iters": iters})
+
+
+def foolsgold(U: torch.Tensor, sizes=None, centre: Optional[torch.Tensor] = None,
+              history: Optional[torch.Tensor] = None, kappa=FOOLSGOLD_KAPPA.default,
+              enable: Optional[torch.Tensor] = None, rounds=0, out: Optional[torch.Tensor] = None) -> AggResult:
+    """FoolsGold (Fung, Yoon & Beschastnikh, RAID 2020; beyond the reference, rule text in docs/PARITY.md), the rule
+    with memory: ``history`` H [n, P] fp32 (None: zeros) holds every row's accumulated updates, H_i <- H_i + (x_i - g)
+    about ``centre`` g, the global model the round started from; the cosines of the NEW histories give every row a
+    weight alpha_i in [0, 1] (``kappa``: the logit's scale) and the result is g + sum_j alpha0_j alpha_j (x_j - g),
+    alpha0 = sizes / sum sizes.  Four launches on the device for n <= 64 (``k_hist_gram``, ``k_gram_reduce``,
+    ``k_foolsgold_weights``, ``k_anchored_rows``), no host read.  ``enable`` (one int32 on the device, None = 1): with 0
+    the new history has the bits of the old one (the caller keeps the old model: a failed round never reaches the
+    history).  ``out``: the buffer the new history goes to (never ``history``).  ``rounds``: the successful rounds
+    accumulated so far.  info = {alpha, max_cos, rounds (a 0-d int64 tensor), history (the new H)}.  Without a centre
+    the result is FedAvg, the history is returned untouched and alpha is all ones.  Always a new tensor."""
+    n = U.shape[0]
+    kappa = FOOLSGOLD_KAPPA.check(kappa, coerce=True)
+    rounds = torch.as_tensor(rounds, dtype=torch.int64).to(U.device)
+    H = torch.zeros_like(U, dtype=torch.float32) if history is None else history
+    if tuple(H.shape) != tuple(U.shape):
+        raise ValueError(f"foolsgold: history {tuple(H.shape)} does not match the rows {tuple(U.shape)}")
+    a = _device_weights(sizes, U.device, n)
+    if centre is None:
+        one = torch.ones(n, dtype=torch.float64, device=U.device)
+        return AggResult(ops.fedavg(U, a if sizes is None else sizes), True, {"alpha": one, "max_cos": torch.zeros_like(one), "rounds": rounds,
+                                                  "history": H})
+    g = centre.to(device=U.device, dtype=torch.float32)
+    Hn, G = ops.hist_gram(U, g, H, enable, out=out)
+    alpha, v, c = ops.foolsgold_weights(G, a / a.sum(), kappa)
+    done = 1 if enable is None else (enable.to(U.device).reshape(()) != 0).to(torch.int64)
+    return AggResult(ops.anchored_rows(U, c, g), True, {"alpha": alpha, "max_cos": v, "rounds": rounds + done,
+                                                         "history": Hn})
 
 
 def dnc(U: torch.Tensor, sizes=None, byz_f=KNOB["byz_f"].default, dnc_iters: int = KNOB["dnc_iters"].default,

@@ -24,9 +24,10 @@ Extensions (all optional, defaults keep reference behaviour):
   synthetic: auto | true | false   (auto = use the reference pickles when present)
   train-size / test-size / seed / har-train-size / har-test-size
 ``server:``
-  mode: the reference's modes plus multi_krum | bulyan | geomed | dnc | cclip (Multi-Krum, Bulyan, the geometric
-        median / RFA, Divide-and-Conquer and centred clipping: defences that assume f >= 1 Byzantine clients;
-        ``krum`` keeps the reference's f = 0, A-11; definitions in docs/PARITY.md)
+  mode: the reference's modes plus multi_krum | bulyan | geomed | dnc | cclip | foolsgold (Multi-Krum, Bulyan, the
+        geometric median / RFA, Divide-and-Conquer and centred clipping: defences that assume f >= 1 Byzantine clients;
+        ``krum`` keeps the reference's f = 0, A-11; FoolsGold: the one rule with memory across rounds, a per-client
+        history of updates whose cosines weigh colluders down; definitions in docs/PARITY.md)
 ``engine:``
   trainer: auto | fused | graph | eager | oracle  (fused = HIP persistent TransformerModel / RNNModel
                                     kernels; graph = HIP-graph-replayed layer programs for CNN/RNN/HAR models;
@@ -63,12 +64,14 @@ Extensions (all optional, defaults keep reference behaviour):
   cclip-iters: int >= 1             (cclip: clipping iterations, all of them run, default 3; 1 = norm bounding)
   cclip-tau: auto | float > 0       (cclip: the clipping radius; auto, the default = the lower median of the rows'
                                     distances to the round's starting model, found on the device every round)
+  foolsgold-kappa: float > 0        (foolsgold: the logit's confidence scale, default 1.0)
   pre-agg: none | nnm | bucketing   (pre-aggregation in front of the rule of ``server.mode``, docs/PARITY.md; default
                                     none.  nnm: every row becomes the mean of its n - f nearest rows, itself included
                                     (f from byz-f, needs n >= 2 f + 3 when explicit); bucketing: the rows are shuffled
                                     with the round's seed and averaged in buckets of bucket-size, and the rule, its
                                     byz-f ``auto`` and its admissibility checks then see the ceil(n / bucket-size)
-                                    bucket means.  Refused for fedavg, hyper, FLTrust and gmm)
+                                    bucket means.  Refused for fedavg, hyper, FLTrust, gmm and foolsgold, whose
+                                    history is keyed by client: mixed rows have no identity)
   bucket-size: int >= 1             (bucketing: rows per bucket, default 2; 1 leaves the rows as they are)
   save-state: bool                  (write {model}.state.pt + {model}.clients.r{rank}.pt every round)
   resume: bool                      (continue from those files: counters, RNGs, optimizer moments)
@@ -83,7 +86,7 @@ from typing import Any, Dict, List, Optional
 import yaml
 
 SERVER_MODES = ("fedavg", "hyper", "FLTrust", "trimmed_mean", "shieldfl", "gmm", "krum", "median", "scionfl",
-                "fltracer", "byzantine", "multi_krum", "bulyan", "geomed", "dnc", "cclip")
+                "fltracer", "byzantine", "multi_krum", "bulyan", "geomed", "dnc", "cclip", "foolsgold")
 ATTACK_MODES = ("Random", "Min-Max", "Min-Sum", "Opt-Fang", "LIE", "AGR-Krum", "AGR-MKrum", "AGR-Bulyan")
 # the AGR-tailored attacks (beyond the reference; docs/PARITY.md) and the rule each one models
 AGR_ATTACK_TARGETS = {"AGR-Krum": "krum", "AGR-MKrum": "mkrum", "AGR-Bulyan": "bulyan"}
@@ -184,9 +187,12 @@ KNOB = {k.kw: k for k in RULE_KNOBS}
 
 # pre-aggregation in front of a robust rule (``engine.pre-agg``; docs/PARITY.md): not rule knobs, the rules never see them
 PRE_AGG_KINDS = ("none", "nnm", "bucketing")
-# FedAvg has its own fused and all-reduce paths, the hypernetwork and FLTrust train, gmm reads per-row attacker flags
-PRE_AGG_REFUSED_MODES = ("fedavg", "hyper", "FLTrust", "gmm")
+# FedAvg has its own fused and all-reduce paths, the hypernetwork and FLTrust train, gmm reads per-row attacker flags,
+# foolsgold keeps a history per client id (a mixed row belongs to no client)
+PRE_AGG_REFUSED_MODES = ("fedavg", "hyper", "FLTrust", "gmm", "foolsgold")
 BUCKET_SIZE = RuleKnob("bucket-size", "bucket_size", "int", 2, 1)
+# foolsgold is stateful and lives outside agg.AGGREGATORS: its knob is not a keyword every rule receives either
+FOOLSGOLD_KAPPA = RuleKnob("foolsgold-kappa", "foolsgold_kappa", "number", 1.0)
 
 EXTENSION_DEFAULTS: Dict[str, Any] = {
     "comm": {"backend": "auto", "address": "", "port": 29517, "clients-per-rank": 0, "one-shot-allgather": "auto",
@@ -197,7 +203,8 @@ EXTENSION_DEFAULTS: Dict[str, Any] = {
                "async-checkpoint": True, "compat-hyper-resume": False, "compat-fltrust": False, "max-retries": 50, "trace": False,
                "phase-sync": False, "fault-inject": [], "save-state": False, "resume": False,
                "speculative": True, "compat-har-train": False, "compat-fedavg-alias": False,
-               **{k.key: k.default for k in RULE_KNOBS}, "pre-agg": "none", BUCKET_SIZE.key: BUCKET_SIZE.default},
+               **{k.key: k.default for k in RULE_KNOBS}, "pre-agg": "none", BUCKET_SIZE.key: BUCKET_SIZE.default,
+               FOOLSGOLD_KAPPA.key: FOOLSGOLD_KAPPA.default},
 }
 
 
@@ -366,6 +373,7 @@ class Config:
         if not isinstance(pre, str) or pre not in PRE_AGG_KINDS:
             raise ValueError(f"engine.pre-agg must be one of {PRE_AGG_KINDS} (got {pre!r})")
         BUCKET_SIZE.check(self.engine.get(BUCKET_SIZE.key, BUCKET_SIZE.default), "engine.")
+        FOOLSGOLD_KAPPA.check(self.engine.get(FOOLSGOLD_KAPPA.key, FOOLSGOLD_KAPPA.default), "engine.")
         if pre != "none" and self.mode in PRE_AGG_REFUSED_MODES:
             raise ValueError(f"engine.pre-agg: {pre} does not apply to server.mode '{self.mode}' (it goes in front of "
                              f"a robust rule; not {', '.join(PRE_AGG_REFUSED_MODES)})")

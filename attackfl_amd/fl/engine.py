@@ -36,9 +36,10 @@ import torch
 
 from .. import ops
 from ..agg import AGGREGATORS, AggResult, pre_aggregate
+from ..agg import foolsgold as agg_foolsgold
 from ..agg import host_info as agg_host_info
 from ..attacks import DistanceEngine, host_info, run_attack
-from ..config import RULE_KNOBS, AttackSpec, Config
+from ..config import FOOLSGOLD_KAPPA, RULE_KNOBS, AttackSpec, Config
 from ..data import DeviceTable, resolve_dataset
 from ..detect import HyperDetector
 from ..eval import Validation
@@ -199,6 +200,7 @@ class EarlyLaunch:
     """An early launch (``FLEngine._early_launch``): what its server step reported and what undoing it needs."""
     g_old: Optional[torch.Tensor]            # the global model before the step
     fl_old: Optional[torch.Tensor]           # FLTrust's server model before the step
+    fg_old: Optional[tuple]                  # foolsgold: (history buffer in use, round count) before the step
     hyper_step: Optional[int]                # the hypernetwork's step count before the step
     snap: tuple                              # (per local client (rng state, training round, genuine), server rng state)
     prep: Optional[Prepared]                 # the next launch's host half, staged ahead
@@ -298,6 +300,13 @@ class FLEngine:
         self.genuine_pool: Optional[torch.Tensor] = None
         self.hyper: Optional[HyperServer] = None
         self.fltrust_model: Optional[torch.Tensor] = None
+        # foolsgold (replicated, every rank its own identical copy): the clients' update histories [n_clients, P] in
+        # two ping-pong buffers (a step reads one and writes the other, so undoing it is switching back), which one is
+        # in use, and the successful rounds accumulated (a 0-d int64 tensor: the device counts in the early launch)
+        self._fg_bufs: Optional[List[torch.Tensor]] = None
+        self._fg_cur = 0
+        self.fg_rounds: Optional[torch.Tensor] = None
+        self._fg_ids = None
         self.detector: Optional[HyperDetector] = None
         self.torch_gen = torch.Generator(device=self.device if self.device.type == "cuda" else "cpu")
         self.torch_gen.manual_seed(self.seed * 31337 + self.rank)
@@ -383,6 +392,10 @@ class FLEngine:
         if self.mode == "FLTrust":
             m = build_model(self.model_name, seed=self.seed + 77)
             self.fltrust_model = self.layout.flatten(m.state_dict(), device=self.device)
+        if self.mode == "foolsgold":
+            self._fg_bufs = [torch.zeros(self.n_clients, self.P, dtype=torch.float32, device=self.device)
+                             for _ in range(2)]
+            self.fg_rounds = torch.zeros((), dtype=torch.int64, device=self.device)
 
     def save_checkpoint(self):
         """Reference ``server.py:551-553`` (same files and keys).  Every rank remembers the saved
@@ -426,6 +439,8 @@ class FLEngine:
                    "rng_state": list(st), "rng_gauss": gauss, "selected": list(self.selected),
                    "global": self.global_params.detach().cpu() if self.global_params is not None else None,
                    "genuine_pool": self.genuine_pool.detach().cpu() if self.genuine_pool is not None else None}
+            if self._fg_bufs is not None:
+                srv.update(fg_history=self.fg_history.detach().cpu(), fg_rounds=int(self.fg_rounds))
             if self.hyper is not None:
                 srv.update(hyper_arena=self.hyper.hnet.arena.detach().cpu(), hyper_m=self.hyper.m.cpu(),
                            hyper_v=self.hyper.v.cpu(), hyper_step=self.hyper.step)
@@ -457,6 +472,9 @@ class FLEngine:
             self.hyper.m.copy_(srv["hyper_m"])
             self.hyper.v.copy_(srv["hyper_v"])
             self.hyper.step = int(srv["hyper_step"])
+        if self._fg_bufs is not None and "fg_history" in srv:
+            self._fg_bufs[self._fg_cur].copy_(srv["fg_history"].to(self.device))
+            self.fg_rounds = torch.as_tensor(int(srv["fg_rounds"]), dtype=torch.int64).to(self.device)
         if os.path.exists(cli_path):
             cli = torch.load(cli_path, weights_only=True, map_location="cpu")
             self.local_params.copy_(cli["params"].to(self.device))
@@ -810,7 +828,8 @@ class FLEngine:
         whose next START models the hypernetwork update generates.  Returns (info, the rule's own success: None =
         always, or a 0-d tensor — gmm).  ``engine.pre-agg`` (nnm, bucketing: ``agg.pre_aggregate``) goes in front of a
         rule of AGGREGATORS on either path.  What a failed early round rolls back stays on ``self`` (``fltrust_model``,
-        ``_trust``, ``_fl_pending``, ``hyper.step``: ``_early_launch_failed``)."""
+        ``_trust``, ``_fl_pending``, ``hyper.step``, foolsgold's history buffer and round count:
+        ``_early_launch_failed``)."""
         mode, g_old = self.mode, self.global_params
         if mode == "hyper":
             self.ckpt_writer.fence()  # the previous round's checkpoint copy of the arena, updated in place below
@@ -822,6 +841,10 @@ class FLEngine:
             new = self._fltrust(U)
             self.global_params = new if ok_all is None else torch.where(ok_all, new, g_old)
             return {}, None
+        if mode == "foolsgold":
+            new, info = self._foolsgold(U, sizes, ok_all)
+            self.global_params = new if ok_all is None else torch.where(ok_all, new, g_old)
+            return info, None
         if mode == "fedavg" and w is not None:
             # the weights were staged with the launch (sizes known then): no host -> device copy here
             if ok_all is None:
@@ -864,6 +887,43 @@ class FLEngine:
         if w is not None and not (U.is_cuda and U.shape[0] == w.shape[0]):
             w = None
         return self._server_step(U, sizes, attackers, None, w=w)[0]
+
+    @property
+    def fg_history(self) -> Optional[torch.Tensor]:
+        """foolsgold: the clients' update histories [n_clients, P], row = client id (None in every other mode)."""
+        return None if self._fg_bufs is None else self._fg_bufs[self._fg_cur]
+
+    def _foolsgold(self, U: torch.Tensor, sizes: torch.Tensor, ok_all: Optional[torch.Tensor]):
+        """FoolsGold (``agg.foolsgold``) on the selected clients' rows about the model the round started from, with the
+        engine's history: read from the buffer in use, written to the other one, which then becomes the one in use.
+        ``ok_all`` goes in as ``enable``, so a round that failed on the device leaves the history's bits (and the count
+        of rounds) as they were.  A selection that is a strict subset of the clients is gathered from and scattered to
+        its rows of the history by client id, the other rows copied.  Before there is a global model (round 1) the
+        result is FedAvg and nothing is accumulated.  -> (the new global model, info)."""
+        H, nxt = self._fg_bufs[self._fg_cur], self._fg_bufs[1 - self._fg_cur]
+        kappa = self.cfg.engine.get(FOOLSGOLD_KAPPA.key, FOOLSGOLD_KAPPA.default)
+        enable = None if ok_all is None else ok_all.all().to(torch.int32).reshape(1)
+        full = list(self.selected) == list(range(self.n_clients))
+        ids = None
+        if not full:
+            key = tuple(self.selected)
+            if self._fg_ids is None or self._fg_ids[0] != key:
+                ix = torch.tensor(self.selected, dtype=torch.long)
+                if self.device.type == "cuda":  # (pinned and non-blocking: no wait for the stream)
+                    from ..ops.layers import upload
+                    ix = upload(ix, self.device)
+                self._fg_ids = (key, ix)
+            ids = self._fg_ids[1]
+        res = agg_foolsgold(U, sizes, centre=self.global_params, history=H if full else H.index_select(0, ids),
+                            kappa=kappa, enable=enable, rounds=self.fg_rounds, out=nxt if full else None)
+        info = {k: v for k, v in res.info.items() if k != "history"}
+        if self.global_params is not None:  # (no centre: the history is untouched)
+            if not full:
+                nxt.copy_(H)
+                nxt.index_copy_(0, ids, res.info["history"])
+            self._fg_cur = 1 - self._fg_cur
+            self.fg_rounds = res.info["rounds"]
+        return res.params, info
 
     def _fltrust_setup(self):
         """Root set (first 200 test rows, ``server.py:290-293``), its device table and the server model's
@@ -1112,12 +1172,12 @@ class FLEngine:
             self.validation.prefetch(g)
 
     def _early_ok(self, last: bool) -> bool:
-        """Which modes launch early (``_early_launch``): FedAvg, the hypernetwork's native update, FLTrust and every
-        rule of AGGREGATORS — all device work without a host read (gmm up to 64 rows)."""
+        """Which modes launch early (``_early_launch``): FedAvg, the hypernetwork's native update, FLTrust, foolsgold
+        (the device decides whether its history advances) and every rule of AGGREGATORS — all device work without a host read (gmm up to 64 rows)."""
         if self.mode == "hyper":
             mode_ok = self.device.type == "cuda" and self.hyper._native_ok()
         else:
-            mode_ok = ((self.mode in ("fedavg", "FLTrust") or self.mode in EARLY_AGGREGATORS)
+            mode_ok = ((self.mode in ("fedavg", "FLTrust", "foolsgold") or self.mode in EARLY_AGGREGATORS)
                        and not (self.mode == "gmm" and len(self.selected) > 64) and not self.fast_fedavg
                        and self.global_params is not None
                        and not self.cfg.engine.get("compat-fedavg-alias", False))
@@ -1163,6 +1223,7 @@ class FLEngine:
         # (the snapshot already includes the staged host half's draws; its clients' START models come out of the
         # hypernetwork update's last launches)
         esl = EarlyLaunch(g_old=self.global_params, fl_old=self.fltrust_model,
+                          fg_old=(self._fg_cur, self.fg_rounds) if self.mode == "foolsgold" else None,
                           hyper_step=self.hyper.step if self.mode == "hyper" else None,
                           snap=([(lc.rng.getstate(), lc.training_round, lc.genuine) for lc in self.local],
                                 self.server_rng.getstate()),
@@ -1207,6 +1268,8 @@ class FLEngine:
             self.fltrust_model = esl.fl_old
             self._trust = None
             self._fl_pending = None
+        if esl.fg_old is not None:  # the device kept the old history's bits: back to the buffer that holds them
+            self._fg_cur, self.fg_rounds = esl.fg_old
         if esl.hyper_step is not None:  # the device skipped the hypernetwork update: its step count too
             self.hyper.step = esl.hyper_step
             self.hyper._info_dev = None

@@ -413,6 +413,36 @@ def anchored_rows(U: torch.Tensor, c: torch.Tensor, anchor: torch.Tensor) -> tor
     return composite.anchored_rows(U, c, anchor)
 
 
+def hist_gram(U: torch.Tensor, g: torch.Tensor, H: torch.Tensor, enable: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None):
+    """FoolsGold's history step -> (H_new, G): H_new = H + (U - g[None]) in fp32 (the bits of that torch expression;
+    ``enable``, one int32 on the device, None = 1: with 0 the bits of H) and G = H_new H_new^T in fp64.  Device,
+    n <= 64: one pass over U, g and H (``k_hist_gram``, then ``k_gram_reduce``), G bit-equal to
+    ``gram_anchored(H_new, zeros)``; H_new goes to ``out`` when given (a second [n, P] fp32 buffer, never H)."""
+    if _dev(U) and 1 <= U.shape[0] <= 64:
+        f32 = lambda t: t.to(device=U.device, dtype=torch.float32).contiguous()
+        en = (torch.ones(1, dtype=torch.int32, device=U.device) if enable is None
+              else enable.to(device=U.device, dtype=torch.int32).reshape(1))
+        Hn = out if out is not None else torch.empty(U.shape, dtype=torch.float32, device=U.device)
+        return Hn, native().hist_gram(f32(U), f32(g), f32(H), en, Hn)
+    Hn, G = composite.hist_gram(U, g, H.to(U.device), enable)
+    if out is not None:
+        Hn = out.copy_(Hn)
+    return Hn, G
+
+
+def foolsgold_weights(G: torch.Tensor, alpha0: torch.Tensor, kappa: float = 1.0):
+    """FoolsGold's weights from the Gram of the histories -> (alpha [n], max cosine v [n], c = alpha0 * alpha [n]), fp64
+    on G's device.  Device, n <= 64: ``k_foolsgold_weights`` (one launch, no host read); the composite beyond."""
+    if not float(kappa) > 0.0:
+        raise ValueError(f"foolsgold_weights: kappa must be a number > 0 (got {kappa!r})")
+    if _dev(G) and G.shape[0] <= 64:
+        out = native().foolsgold_weights(G.to(torch.float64).contiguous(),
+                                         alpha0.to(device=G.device, dtype=torch.float64).contiguous(), float(kappa))
+        return out[0], out[1], out[2]
+    return composite.foolsgold_weights(G, alpha0.to(G.device), float(kappa))
+
+
 def centred_gram(U: torch.Tensor) -> torch.Tensor:
     """n x n Gram of the rows centred on their mean (fp64).  Device, n <= 64: the fp64-MFMA Gram pass of ``agg.hip``
     (rows centred on one of them, then double-centred) instead of a generic fp64 GEMM with M = N = n and

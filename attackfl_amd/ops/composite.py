@@ -388,6 +388,50 @@ def anchored_rows(U: torch.Tensor, c: torch.Tensor, anchor: torch.Tensor) -> tor
     return (g + acc).to(U.dtype)
 
 
+def hist_gram(U: torch.Tensor, g: torch.Tensor, H: torch.Tensor, enable: Optional[torch.Tensor] = None):
+    """FoolsGold's history step (``k_hist_gram``; rule text in docs/PARITY.md): H_new = H + (U - g[None]) in fp32, the
+    difference rounded first and the sum second; ``enable`` (one int32, None = 1) of 0 keeps the bits of H -> (H_new, a
+    new tensor, and the Gram H_new H_new^T in fp64).  Tensor ops only (no host read)."""
+    H = H.to(torch.float32)
+    Hn = H + (U.to(torch.float32) - g.to(device=U.device, dtype=torch.float32)[None, :])
+    if enable is not None:
+        Hn = torch.where(enable.to(H.device).reshape(()) != 0, Hn, H)
+    return Hn, gram_anchored(Hn, torch.zeros_like(Hn[0]))
+
+
+def foolsgold_weights(G: torch.Tensor, alpha0: torch.Tensor, kappa: float):
+    """FoolsGold's weights from the Gram of the histories (``k_foolsgold_weights``; rule text in docs/PARITY.md):
+    cosines cs_ij (0 for a pair with a zero or non-finite norm, clamped to [-1, 1]), v_i = max_{j != i} cs_ij, pardoning
+    cs_ij v_i / v_j where v_j > v_i (a v_j of exactly 0 pardons nothing), a_i = clamp(1 - max_{j != i} cs'_ij, 0, 1),
+    rescaled by their maximum M (M <= 0: every alpha is 0), an a_i of exactly 1 -> 0.99, alpha_i =
+    clamp(kappa (ln(a_i / (1 - a_i)) + 0.5), 0, 1); one row: alpha = 1, v = 0 -> (alpha, v, alpha0 * alpha), fp64 [n].
+    Tensor ops only (no host read), so it also serves device tensors beyond the kernel's 64 rows."""
+    G, a0 = G.double(), alpha0.double()
+    n = G.shape[0]
+    if n == 1:
+        one = torch.ones(1, dtype=torch.float64, device=G.device)
+        return one, torch.zeros_like(one), a0 * one
+    diag = G.diagonal()
+    zero = torch.zeros((), dtype=torch.float64, device=G.device)
+    nrm = torch.where(torch.isfinite(diag) & (diag > 0), diag.clamp_min(0.0).sqrt(), zero)
+    live = (nrm[:, None] > 0) & (nrm[None, :] > 0)
+    den = nrm[:, None] * nrm[None, :]
+    cs = torch.where(live, G / torch.where(live, den, torch.ones_like(den)), zero).clamp(-1.0, 1.0)
+    off = ~torch.eye(n, dtype=torch.bool, device=G.device)
+    ninf = torch.full_like(cs, float("-inf"))
+    v = torch.where(off, cs, ninf).max(dim=1).values
+    vi, vj = v[:, None].expand(n, n), v[None, :].expand(n, n)
+    pard = (vj > vi) & (vj != 0)
+    csp = torch.where(pard, cs * vi / torch.where(pard, vj, torch.ones_like(vj)), cs)
+    a = (1.0 - torch.where(off, csp, ninf).max(dim=1).values).clamp(0.0, 1.0)
+    M = a.max()
+    a = a / torch.where(M > 0, M, torch.ones_like(M))
+    a = torch.where(a == 1.0, torch.full_like(a, 0.99), a)
+    alpha = (float(kappa) * (torch.log(a / (1.0 - a)) + 0.5)).clamp(0.0, 1.0)
+    alpha = torch.where(M > 0, alpha, torch.zeros_like(alpha))
+    return alpha, v, a0 * alpha
+
+
 def top_pc(G: torch.Tensor) -> torch.Tensor:
     """First principal-component scores v sqrt(lambda) from the centred Gram (``k_top_pc``, up to the sign)."""
     ev, V = torch.linalg.eigh(G)

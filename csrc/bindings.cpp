@@ -345,6 +345,46 @@ torch::Tensor anchored_rows(torch::Tensor U, torch::Tensor c, torch::Tensor anch
   return out;
 }
 
+// FoolsGold (agg.foolsgold).  hist_gram: U, H [K <= 64, P] fp32, g [P] fp32, enable [1] int32 (device), Hnew [K, P] fp32
+// (a buffer other than H) -> the Gram [K, K] fp64 of Hnew = H + (U - g) (enable 0: = H), which the pass also writes
+torch::Tensor hist_gram(torch::Tensor U, torch::Tensor g, torch::Tensor H, torch::Tensor enable, torch::Tensor Hnew) {
+  check_dev(U, "U", torch::kFloat32);
+  check_dev(g, "g", torch::kFloat32);
+  check_dev(H, "H", torch::kFloat32);
+  check_dev(Hnew, "Hnew", torch::kFloat32);
+  check_dev(enable, "enable", torch::kInt32);
+  TORCH_CHECK(U.dim() == 2 && U.size(0) >= 1 && U.size(0) <= 64 && U.size(1) >= 1, "hist_gram: U [K <= 64, P >= 1]");
+  const int K = U.size(0);
+  const long P = U.size(1);
+  TORCH_CHECK(H.sizes() == U.sizes() && Hnew.sizes() == U.sizes() && g.dim() == 1 && g.size(0) == P &&
+              enable.numel() == 1, "hist_gram: H, Hnew [K, P], g [P], enable [1] (got H ", H.sizes(), ", Hnew ",
+              Hnew.sizes(), ", g ", g.sizes(), " for U ", U.sizes(), ")");
+  TORCH_CHECK(g.device() == U.device() && H.device() == U.device() && Hnew.device() == U.device() &&
+              enable.device() == U.device(), "hist_gram: every tensor on U's device");
+  TORCH_CHECK(Hnew.data_ptr() != H.data_ptr() && Hnew.data_ptr() != U.data_ptr(), "hist_gram: Hnew is a second buffer");
+  auto gram = torch::empty({K, K}, U.options().dtype(torch::kFloat64));
+  auto scratch = gram_scratch(U);
+  TORCH_CHECK(afl_hist_gram(U.data_ptr<float>(), g.data_ptr<float>(), H.data_ptr<float>(), Hnew.data_ptr<float>(), K, P,
+                            enable.data_ptr<int>(), scratch.data_ptr<double>(), gram.data_ptr<double>(), cur()) == 0,
+              "hist_gram launch failed");
+  AFL_CHECK_LAUNCH();
+  return gram;
+}
+
+// foolsgold_weights: G [n, n], alpha0 [n] fp64, kappa > 0 -> [3, n] fp64 {alpha, max cosine, alpha0 * alpha}
+torch::Tensor foolsgold_weights(torch::Tensor G, torch::Tensor alpha0, double kappa) {
+  check_dev(G, "G", torch::kFloat64);
+  check_dev(alpha0, "alpha0", torch::kFloat64);
+  const int64_t n = check_square64(G, "foolsgold_weights: G [n, n], alpha0 [n], n <= 64");
+  TORCH_CHECK(alpha0.numel() == n && alpha0.device() == G.device(), "foolsgold_weights: alpha0 [n] on G's device");
+  TORCH_CHECK(kappa > 0.0, "foolsgold_weights: kappa > 0 (got ", kappa, ")");
+  auto out = torch::empty({3, n}, G.options());
+  TORCH_CHECK(afl_foolsgold_weights(G.data_ptr<double>(), alpha0.data_ptr<double>(), (int)n, kappa,
+                                    out.data_ptr<double>(), cur()) == 0, "foolsgold_weights launch failed");
+  AFL_CHECK_LAUNCH();
+  return out;
+}
+
 // Gram matrix of the rows centred on the MEAN row (PCA of the updates: agg.fltracer / agg.gmm), through the same
 // fp64-MFMA pass (H: the Gram of the rows centred on the pass's final centre row, the scratch tail) followed by the
 // double centring C = H - rowmean - colmean + mean, which does not depend on the centre beyond rounding
@@ -1048,6 +1088,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gram_anchored", &gram_anchored);
   m.def("cclip_weights", &cclip_weights);
   m.def("anchored_rows", &anchored_rows);
+  m.def("hist_gram", &hist_gram);
+  m.def("foolsgold_weights", &foolsgold_weights);
   m.def("fxsum_test", &fxsum_test);
   m.def("tf2_wgs_per_client", &afl_tf2_wgs_per_client);
   m.def("gram_centred", &gram_centred);

@@ -492,6 +492,13 @@ int afl_gram_anchored(const float* U, int K, long P, const float* anchor, double
 int afl_cclip_weights(const double* G, const double* alpha, const double* c0, int n, int iters, double tau, double* c,
                       double* info, hipStream_t s);
 int afl_anchored_rows(const float* U, const double* c, int N, long P, const float* g, float* out, hipStream_t s);
+// FoolsGold (docs/PARITY.md).  afl_hist_gram (agg.hip k_hist_gram + k_gram_reduce): Hnew = Hold + (U - g) in fp32
+// (*enable == 0: the bits of Hold; enable nullptr = 1) into a second buffer and gram [K][K] = Hnew Hnew^T, bit-equal to
+// afl_gram_anchored(Hnew, zeros); K <= 64, partial: afl_gram_partials(K, P) doubles.  afl_foolsgold_weights
+// (k_foolsgold_weights): G [n][n], alpha0 [n] fp64, kappa > 0 -> out [3][n] = {alpha, max cosine v, alpha0 * alpha}.
+int afl_hist_gram(const float* U, const float* g, const float* Hold, float* Hnew, int K, long P, const int* enable,
+                  double* partial, double* gram, hipStream_t s);
+int afl_foolsgold_weights(const double* G, const double* alpha0, int n, double kappa, double* out, hipStream_t s);
 // Divide-and-Conquer (DnC, docs/PARITY.md) on U [K <= 64][P] fp32.  afl_dnc_gram (agg.hip k_dnc_gram): for each of
 // ``iters`` iterations the tile-pair partials of the Gram of the rows centred on row 0, over the b keyed columns of
 // that iteration (all P in natural order when b >= P) -> partial, afl_dnc_partials(K, P, b, iters) doubles.

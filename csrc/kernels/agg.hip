@@ -18,11 +18,15 @@
 //   geomed_weights  smoothed Weiszfeld (geometric median, RFA) in Gram space
 //   cclip_weights   centred clipping in Gram space (anchored Gram: gram_f64 about the previous global model)
 //   anchored_rows   out = g + sum_i c_i (U_i - g) (fp64 weights, fp64 accumulate): centred clipping's row pass
+//   hist_gram       FoolsGold: H_new = H_old + (U - g) and the fp64-MFMA Gram of H_new in one sweep (gram_f64's tile body)
+//   foolsgold_weights  FoolsGold: cosines, pardoning and the logit weights from that Gram, one wave
 //   dnc_gram        DnC: fp64-MFMA Grams over keyed random column subsets, all iterations in one launch
 //   dnc_select      DnC: top eigenpair, scores, ranked drop, mask intersection and weights, one wave
-// Shared: gram_for_tiles (the host's one T = 1 .. 4 launch of gram_f64 and dnc_gram) and lds_load_square (the matrix load
-// of geomed_weights and cclip_weights).  The device code of the two Gram kernels and of the one-wave kernels is otherwise
-// kept per kernel: folding it cost 0.2 - 3 % in single-call timings (profiles/ab_agg_refactor.md).
+// Shared: gram_for_tiles (the host's one T = 1 .. 4 launch of gram_f64, hist_gram and dnc_gram), gram_tile_mfma and
+// gram_block_partials (the tile body of gram_f64 and hist_gram, whose Grams must agree bit for bit) and lds_load_square
+// (the matrix load of geomed_weights, cclip_weights and foolsgold_weights).  The device code of gram_f64 and dnc_gram
+// and of the one-wave kernels is otherwise kept per kernel: folding it cost 0.2 - 3 % in single-call timings
+// (profiles/ab_agg_refactor.md).
 //
 // Every reduction is two-pass with a fixed summation order (no float atomics), so results are
 // bit-identical across ranks: the replicated server state on each rank stays in lock-step.
@@ -231,6 +235,35 @@ int afl_pair_sqdist(const float* G, int K, long P, double* partial, double* D, h
 constexpr int GR_CH = 1024;
 typedef double d4v __attribute__((ext_vector_type(4)));
 
+// The tile body that k_gram_f64 and k_hist_gram share, stated once.  gram_tile_mfma: one 16-column step of a wave, the
+// T (T + 1) / 2 tile pairs in (ti, tj >= ti) order, 4 MFMAs each (q = the k index).  gram_block_partials: the fixed-order
+// reduction over the block's 4 waves into its row of ``partial`` (red: the block's [4][NP * 256] LDS buffer).
+template <int T>
+__device__ __forceinline__ void gram_tile_mfma(const double (&x)[T][4], d4v (&acc)[T * (T + 1) / 2]) {
+  int p = 0;
+#pragma unroll
+  for (int ti = 0; ti < T; ++ti)
+#pragma unroll
+    for (int tj = ti; tj < T; ++tj, ++p)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[ti][q], x[tj][q], acc[p], 0, 0, 0);
+}
+
+template <int NP>
+__device__ __forceinline__ void gram_block_partials(const d4v (&acc)[NP], double (&red)[4][NP * 256],
+                                                    double* __restrict__ partial) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r16 = lane & 15, grp = lane >> 4;
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wave][p * 256 + (grp + 4 * r) * 16 + r16] = acc[p][r];
+  __syncthreads();
+  for (int e = threadIdx.x; e < NP * 256; e += 256)
+    partial[(long)blockIdx.x * NP * 256 + e] = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
+}
+
 template <int T>
 __global__ void __launch_bounds__(256) k_gram_f64(const float* __restrict__ G, int K, long P,
                                                   const int* __restrict__ centre, double* __restrict__ partial,
@@ -262,23 +295,57 @@ __global__ void __launch_bounds__(256) k_gram_f64(const float* __restrict__ G, i
       for (int q = 0; q < 4; ++q)
         x[t][q] = (row < K && c0 + q < P) ? (double)G[(long)row * P + c0 + q] - ctr[q] : 0.0;
     }
-    int p = 0;
-#pragma unroll
-    for (int ti = 0; ti < T; ++ti)
-#pragma unroll
-      for (int tj = ti; tj < T; ++tj, ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[ti][q], x[tj][q], acc[p], 0, 0, 0);
+    gram_tile_mfma<T>(x, acc);
   }
-  // fixed-order reduction over the 4 waves
+  gram_block_partials<NP>(acc, red, partial);
+}
+
+// FoolsGold's history pass (rule text in docs/PARITY.md): H_new = H_old + (U - g) in fp32, the difference rounded
+// first and the sum second (no multiply, so nothing to contract: the bits of torch's H + (U - g[None])), written to a
+// second buffer, and the Gram partials of H_new in the same sweep.  The walk is k_gram_f64's with an anchor: every
+// (row, column) is loaded by exactly one lane of one block, which is also its one writer, and the MFMA operand is
+// (double)H_new, what k_gram_f64 forms from H_new about a zero anchor, so after k_gram_reduce the Gram is bit-equal to
+// afl_gram_anchored(H_new, zeros).  *enable == 0 (a failed round, decided on the device): H_new takes the bits of H_old,
+// selected, not added to zero, and a faulted row's NaN never reaches the history.
+template <int T>
+__global__ void __launch_bounds__(256) k_hist_gram(const float* __restrict__ U, const float* __restrict__ g,
+                                                   const float* __restrict__ Hold, float* __restrict__ Hnew, int K,
+                                                   long P, const int* __restrict__ enable,
+                                                   double* __restrict__ partial) {
+  constexpr int NP = T * (T + 1) / 2;
+  __shared__ double red[4][NP * 256];
+  const bool en = enable == nullptr || *enable != 0;  // (block-uniform)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r16 = lane & 15, grp = lane >> 4;
+  d4v acc[NP];
 #pragma unroll
-  for (int p = 0; p < NP; ++p)
+  for (int p = 0; p < NP; ++p) acc[p] = d4v{0.0, 0.0, 0.0, 0.0};
+  const long c_begin = (long)blockIdx.x * GR_CH + wave * (GR_CH / 4);
+  for (int st = 0; st < GR_CH / 4 / 16; ++st) {
+    const long c0 = c_begin + st * 16 + grp * 4;
+    double x[T][4];
+    float ctr[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) red[wave][p * 256 + (grp + 4 * r) * 16 + r16] = acc[p][r];
-  __syncthreads();
-  for (int e = threadIdx.x; e < NP * 256; e += 256)
-    partial[(long)blockIdx.x * NP * 256 + e] = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
+    for (int q = 0; q < 4; ++q) ctr[q] = c0 + q < P ? g[c0 + q] : 0.f;
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      const int row = t * 16 + r16;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        x[t][q] = 0.0;
+        if (row < K && c0 + q < P) {
+          const long e = (long)row * P + c0 + q;
+          const float h = Hold[e];
+          const float d = U[e] - ctr[q];
+          const float hn = en ? h + d : h;
+          Hnew[e] = hn;
+          x[t][q] = (double)hn;
+        }
+      }
+    }
+    gram_tile_mfma<T>(x, acc);
+  }
+  gram_block_partials<NP>(acc, red, partial);
 }
 
 // The centre of pass 2 from pass 1's distances (the end of pass 1's k_gram_reduce, after D1 is formed): the row closest to
@@ -422,6 +489,24 @@ int afl_gram_anchored(const float* U, int K, long P, const float* anchor, double
                       hipStream_t s) {
   if (K < 1 || K > GR_MAXK || P < 1 || anchor == nullptr) return (int)hipErrorInvalidValue;
   gram_pass(U, K, P, nullptr, partial, gram, nullptr, nullptr, s, anchor);
+  return (int)hipGetLastError();
+}
+
+// FoolsGold's history update and the Gram of the new history: k_hist_gram, then the Gram pass's own k_gram_reduce.
+// Hnew is a second buffer ([K][P], not Hold: the caller keeps the old history until the round is known to have
+// succeeded); ``partial``: afl_gram_partials(K, P) doubles; ``enable``: a device word or nullptr (= 1).
+int afl_hist_gram(const float* U, const float* g, const float* Hold, float* Hnew, int K, long P, const int* enable,
+                  double* partial, double* gram, hipStream_t s) {
+  if (K < 1 || K > GR_MAXK || P < 1 || U == nullptr || g == nullptr || Hold == nullptr || Hnew == nullptr ||
+      Hold == Hnew)
+    return (int)hipErrorInvalidValue;
+  const int nb = afl_cdiv(P, GR_CH);
+  gram_for_tiles(K, [&](auto t) {
+    hipLaunchKernelGGL(k_hist_gram<decltype(t)::value>, dim3(nb), dim3(256), 0, s, U, g, Hold, Hnew, K, P, enable,
+                       partial);
+  });
+  hipLaunchKernelGGL(k_gram_reduce, dim3(1), dim3(256), 0, s, partial, nb, K, (K + 15) / 16, nullptr, gram, nullptr,
+                     nullptr);
   return (int)hipGetLastError();
 }
 
@@ -1740,5 +1825,69 @@ __global__ void __launch_bounds__(256) k_anchored_rows(const float* __restrict__
 int afl_anchored_rows(const float* U, const double* c, int N, long P, const float* g, float* out, hipStream_t s) {
   if (N < 1 || P < 1) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_anchored_rows, dim3(afl_cdiv(P, 256)), dim3(256), 0, s, U, c, N, P, g, out);
+  return (int)hipGetLastError();
+}
+
+// ============================================================================ foolsgold_weights
+// FoolsGold (Fung, Yoon & Beschastnikh, RAID 2020; rule text in docs/PARITY.md) from the Gram G = H H^T of the n <= 64
+// clients' histories:
+//     cs_ij = clamp(G_ij / (sqrt(G_ii) sqrt(G_jj)), -1, 1) for i != j, 0 for a pair with a zero or non-finite norm
+//     v_i = max_{j != i} cs_ij;  cs'_ij = cs_ij v_i / v_j where v_j > v_i (and v_j != 0), else cs_ij
+//     a_i = clamp(1 - max_{j != i} cs'_ij, 0, 1), M = max_i a_i;  M <= 0: every alpha_i = 0, otherwise a_i <- a_i / M,
+//     an a_i of exactly 1 becomes 0.99, alpha_i = clamp(kappa (ln(a_i / (1 - a_i)) + 0.5), 0, 1);  n = 1: alpha = 1, v = 0
+// One wave, lane i owns row i of G in LDS (row stride n_max + 1): the two row maxima are per-lane loops over the n
+// columns, M is an xor butterfly, which leaves the same bits on every lane; every trip count is fixed by n.
+// out [3][n] = {alpha, v, c = alpha0 * alpha (the weights of anchored_rows)}.
+__global__ void __launch_bounds__(64) k_foolsgold_weights(const double* __restrict__ G, const double* __restrict__ alpha0,
+                                                          int n, double kappa, double* __restrict__ out) {
+  __shared__ double A[GMM_MAXN * KS_LD], nb[GMM_MAXN], vb[GMM_MAXN];
+  const int i = threadIdx.x;
+  lds_load_square(A, KS_LD, G, n);
+  __syncthreads();
+  const double gii = i < n ? A[i * KS_LD + i] : 0.0;
+  nb[i] = gram_finite(gii) && gii > 0.0 ? sqrt(gii) : 0.0;  // (0: the row's pairs get cs = 0)
+  __syncthreads();
+  const double* row = A + (i < n ? i : 0) * KS_LD;
+  const double mi = nb[i];
+  double v = -INFINITY;
+  for (int j = 0; j < n; ++j) {
+    const double nj = nb[j];
+    double cs = mi > 0.0 && nj > 0.0 ? row[j] / (mi * nj) : 0.0;
+    cs = cs > 1.0 ? 1.0 : (cs < -1.0 ? -1.0 : cs);
+    v = j != i && cs > v ? cs : v;
+  }
+  v = i < n && n > 1 ? v : 0.0;
+  vb[i] = v;
+  __syncthreads();
+  double m = -INFINITY;
+  for (int j = 0; j < n; ++j) {
+    const double nj = nb[j], vj = vb[j];
+    double cs = mi > 0.0 && nj > 0.0 ? row[j] / (mi * nj) : 0.0;
+    cs = cs > 1.0 ? 1.0 : (cs < -1.0 ? -1.0 : cs);
+    cs = vj > v && vj != 0.0 ? cs * v / vj : cs;
+    m = j != i && cs > m ? cs : m;
+  }
+  double a = 1.0 - m;
+  a = a > 1.0 ? 1.0 : (a > 0.0 ? a : 0.0);  // (a NaN, which no finite Gram gives, counts as 0)
+  a = i < n ? a : 0.0;
+  const double M = wave_max(a);
+  double al = 0.0;
+  if (M > 0.0) {  // (uniform)
+    a = a / M;
+    a = a == 1.0 ? 0.99 : a;
+    al = kappa * (log(a / (1.0 - a)) + 0.5);
+    al = al > 1.0 ? 1.0 : (al > 0.0 ? al : 0.0);
+  }
+  al = n == 1 ? 1.0 : al;
+  if (i < n) {
+    out[i] = al;
+    out[n + i] = v;
+    out[2 * n + i] = alpha0[i] * al;
+  }
+}
+
+int afl_foolsgold_weights(const double* G, const double* alpha0, int n, double kappa, double* out, hipStream_t s) {
+  if (n < 1 || n > GMM_MAXN || !(kappa > 0.0)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_foolsgold_weights, dim3(1), dim3(64), 0, s, G, alpha0, n, kappa, out);
   return (int)hipGetLastError();
 }

@@ -95,6 +95,9 @@ def run_cell(mode: str, attack: str, device: str, rounds: int, threads: int = 0,
             "gamma_succ": [round(r["attack"]["gamma_succ"], 4) for r in ok if "gamma_succ" in r.get("attack", {})],
             # every tried γ of the last attacking round (the reference prints each, src/Utils.py:119)
             "gammas_last": next((r["attack"]["gammas"] for r in reversed(hist) if "gammas" in r.get("attack", {})), None),
+            # foolsgold: every client's weight, averaged over the successful rounds that had a history, and the last one
+            **({"alpha_mean": [round(sum(r["alpha"][i] for r in ok[1:]) / max(1, len(ok) - 1), 4) for i in range(8)],
+                "alpha_last": [round(a, 4) for a in ok[-1]["alpha"]]} if ok and "alpha" in ok[-1] else {}),
             "seconds": round(time.time() - t0, 2)}
 
 
