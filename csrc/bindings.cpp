@@ -705,7 +705,7 @@ void hyper_adam_outer(torch::Tensor W, torch::Tensor b, torch::Tensor m, torch::
   const int H = W.size(1);
   TORCH_CHECK(m.numel() >= P * H + P && v.numel() >= P * H + P, "moment buffers too small");
   afl_hyper_adam(W.data_ptr<float>(), b.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
-                 delta.data_ptr<float>(), f.data_ptr<float>(), P, H, (int)step, (float)lr, (float)b1, (float)b2,
+                 delta.data_ptr<float>(), f.data_ptr<float>(), P, H, (int)step, (float)lr, b1, b2,
                  (float)eps, (float)scale, cur());
   AFL_CHECK_LAUNCH();
 }
@@ -776,8 +776,8 @@ std::vector<torch::Tensor> hyper_server_update(torch::Tensor arena, torch::Tenso
   auto feat = torch::empty({2 * 128}, opt);
   auto info = torch::empty({n, 2}, opt);
   afl_hyper_server_update(arena.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), U.data_ptr<float>(),
-                          ur.data(), cl.data(), n, d, offW, offB, P, (int)step0, (float)lr, (float)clip, (float)b1,
-                          (float)b2, (float)eps, delta.data_ptr<float>(), partial.data_ptr<float>(),
+                          ur.data(), cl.data(), n, d, offW, offB, P, (int)step0, (float)lr, (float)clip, b1, b2,
+                          (float)eps, delta.data_ptr<float>(), partial.data_ptr<float>(),
                           feat.data_ptr<float>(), info.data_ptr<float>(), en, gl.data(), ng, gfeat.data_ptr<float>(),
                           gout.data_ptr<float>(), cur());
   AFL_CHECK_LAUNCH();

@@ -28,7 +28,7 @@ int afl_hyper_nblocks(long P);
 void afl_hyper_rows(const float* W, const float* b, const float* f, const float* u, long P, int H, float* out,
                     float* partial, float* dfeat, hipStream_t s);
 void afl_hyper_adam(float* W, float* bvec, float* m, float* v, const float* delta, const float* f, long P, int H,
-                    int step, float lr, float b1, float b2, float eps, float gs, hipStream_t s);
+                    int step, float lr, double b1, double b2, float eps, float gs, hipStream_t s);
 // arena offsets (floats) of the hypernet embedding + MLP (L layers, E -> H -> ... -> H)
 struct HySmallDesc {
   long emb;
@@ -38,9 +38,9 @@ struct HySmallDesc {
 };
 void afl_hyper_server_update(float* A, float* m, float* v, const float* U, const long* urow, const int* clients,
                              int n, const HySmallDesc& d, long offW, long offB, long P, int step0, float lr,
-                             float clip, float b1, float b2, float eps, float* delta, float* partial, float* feat,
+                             float clip, double b1, double b2, float eps, float* delta, float* partial, float* feat,
                              float* info, const int* enable, const int* gen, int ngen, float* gen_feat,
-                             float* gen_out, hipStream_t s);
+                             float* gen_out, hipStream_t s);  // betas in double: see hy_coefs
 // W f_c + b of n clients (feat [n, H]) -> out [n, P]: one sweep over the heads per 32 clients
 void afl_hyper_generate(const float* A, const HySmallDesc& d, long offW, long offB, long P, const float* feat, int n,
                         float* out, hipStream_t s);

@@ -162,8 +162,8 @@ void afl_hyper_rows(const float* W, const float* b, const float* f, const float*
 __global__ void __launch_bounds__(256) k_hyper_adam(float* __restrict__ W, float* __restrict__ bvec,
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     const float* __restrict__ delta, const float* __restrict__ f,
-                                                    long P, int H, float lr_bc1, float rsqrt_bc2, float b1, float b2,
-                                                    float eps, float gs) {
+                                                    long P, int H, float lr_bc1, float rsqrt_bc2, float c1, float b2,
+                                                    float c2, float eps, float gs) {  // c = 1 - beta (hy_coefs)
   const long nW = P * H;
   const long total = nW + P;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -177,8 +177,8 @@ __global__ void __launch_bounds__(256) k_hyper_adam(float* __restrict__ W, float
       g = gs * delta[i - nW];
       p = bvec[i - nW];
     }
-    float mi = m[i] + (1.f - b1) * (g - m[i]);
-    float vi = b2 * v[i] + (1.f - b2) * g * g;
+    float mi = m[i] + c1 * (g - m[i]);
+    float vi = b2 * v[i] + c2 * g * g;
     m[i] = mi;
     v[i] = vi;
     p -= lr_bc1 * mi / (sqrtf(vi) * rsqrt_bc2 + eps);
@@ -187,13 +187,23 @@ __global__ void __launch_bounds__(256) k_hyper_adam(float* __restrict__ W, float
   }
 }
 
+// Adam's per-step scalars from the betas in double: the complements 1 - beta are rounded to fp32 once, here
+// (1.f - fp32(0.999) is 1.3e-5 away from 0.001), and the bias corrections use the same double betas
+struct HyCoefs {
+  float lr_bc1, rbc2, c1, b2, c2;
+};
+static HyCoefs hy_coefs(double lr, double b1, double b2, int step) {
+  const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);
+  return {(float)(lr / bc1), (float)(1.0 / sqrt(bc2)), (float)(1.0 - b1), (float)b2, (float)(1.0 - b2)};
+}
+
 void afl_hyper_adam(float* W, float* bvec, float* m, float* v, const float* delta, const float* f, long P, int H,
-                    int step, float lr, float b1, float b2, float eps, float gs, hipStream_t s) {
-  double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
+                    int step, float lr, double b1, double b2, float eps, float gs, hipStream_t s) {
+  const HyCoefs k = hy_coefs(lr, b1, b2, step);
   long total = P * H + P;
   int nb = (int)min(8192L, (total + 255) / 256);
-  hipLaunchKernelGGL(k_hyper_adam, dim3(nb), dim3(256), 0, s, W, bvec, m, v, delta, f, P, H, (float)(lr / bc1),
-                     (float)(1.0 / sqrt(bc2)), b1, b2, eps, gs);
+  hipLaunchKernelGGL(k_hyper_adam, dim3(nb), dim3(256), 0, s, W, bvec, m, v, delta, f, P, H, k.lr_bc1, k.rbc2, k.c1,
+                     k.b2, k.c2, eps, gs);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -302,11 +312,13 @@ __device__ void hs_forward(const float* sm, const HySmallDesc& d, int c, float (
 // Adam on one element (gradient already scaled).  Every fused multiply-add is spelled out: the head update runs
 // in three kernels (k_hyper_adam_v, k_hyper_adam_rows4, k_hyper_gen4) that must agree bitwise, which the
 // compiler's own contraction choices do not promise across differently shaped kernels.
+// c1 = 1 - beta1 and c2 = 1 - beta2 come from the host, rounded from double (hy_coefs): 1.f - fp32(0.999) is off
+// by 1.3e-5 relative, which the second moment then carries (torch.optim.Adam rounds 1 - beta2 itself).
 __device__ __forceinline__ float hs_adam(float p, float g, float& mm, float& vv, float lr_bc1, float rsqrt_bc2,
-                                         float b1, float b2, float eps) {
+                                         float c1, float b2, float c2, float eps) {
 #pragma clang fp contract(off)  // (g - mm must not absorb the caller's product that formed g)
-  mm = __builtin_fmaf(1.f - b1, g - mm, mm);
-  vv = __builtin_fmaf((1.f - b2) * g, g, b2 * vv);
+  mm = __builtin_fmaf(c1, g - mm, mm);
+  vv = __builtin_fmaf(c2 * g, g, b2 * vv);
   return p - (lr_bc1 * mm) / __builtin_fmaf(__builtin_sqrtf(vv), rsqrt_bc2, eps);
 }
 
@@ -315,9 +327,9 @@ __global__ void __launch_bounds__(HS_NT) k_hyper_small(float* __restrict__ A, fl
                                                        float* __restrict__ v, const float* __restrict__ partial,
                                                        int nb, int ci, int cj, float* __restrict__ feat_j,
                                                        float* __restrict__ info, HySmallDesc d, long nsmall,
-                                                       float clip, float lr_bc1, float rsqrt_bc2, float b1, float b2,
-                                                       float eps, const int* __restrict__ enable, HyClients gen,
-                                                       int ngen, float* __restrict__ gen_feat) {
+                                                       float clip, float lr_bc1, float rsqrt_bc2, float c1, float b2,
+                                                       float c2, float eps, const int* __restrict__ enable,
+                                                       HyClients gen, int ngen, float* __restrict__ gen_feat) {
   // enable (device word, optional): 0 = the round failed, leave the hypernetwork untouched (the engine enqueues
   // the update before it knows; FLEngine._early_launch).  gen / ngen: after the update, the MLP features of the
   // next generation's clients -> gen_feat [ngen, H] (from the untouched MLP when the update is disabled)
@@ -459,10 +471,10 @@ __global__ void __launch_bounds__(HS_NT) k_hyper_small(float* __restrict__ A, fl
           }
         }
         float4 p = s4[c];
-        p.x = hs_adam(p.x, g.x, pm[i].x, pv[i].x, lr_bc1, rsqrt_bc2, b1, b2, eps);
-        p.y = hs_adam(p.y, g.y, pm[i].y, pv[i].y, lr_bc1, rsqrt_bc2, b1, b2, eps);
-        p.z = hs_adam(p.z, g.z, pm[i].z, pv[i].z, lr_bc1, rsqrt_bc2, b1, b2, eps);
-        p.w = hs_adam(p.w, g.w, pm[i].w, pv[i].w, lr_bc1, rsqrt_bc2, b1, b2, eps);
+        p.x = hs_adam(p.x, g.x, pm[i].x, pv[i].x, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+        p.y = hs_adam(p.y, g.y, pm[i].y, pv[i].y, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+        p.z = hs_adam(p.z, g.z, pm[i].z, pv[i].z, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+        p.w = hs_adam(p.w, g.w, pm[i].w, pv[i].w, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
         m4[c] = pm[i];
         v4[c] = pv[i];
         A4[c] = p;
@@ -474,7 +486,7 @@ __global__ void __launch_bounds__(HS_NT) k_hyper_small(float* __restrict__ A, fl
     for (long e = tid; e < nemb; e += HS_NT) {
       const int row = (int)(e / E), col = (int)(e - (long)row * E);
       float mm = m[d.emb + e], vv = v[d.emb + e];
-      const float p = hs_adam(sm[e], row == ci ? gs * gemb[col] : 0.f, mm, vv, lr_bc1, rsqrt_bc2, b1, b2, eps);
+      const float p = hs_adam(sm[e], row == ci ? gs * gemb[col] : 0.f, mm, vv, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
       m[d.emb + e] = mm;
       v[d.emb + e] = vv;
       A[d.emb + e] = p;
@@ -506,10 +518,10 @@ __global__ void __launch_bounds__(HS_NT) k_hyper_small(float* __restrict__ A, fl
             const int o = (int)(4 * e4 / din), k = (int)(4 * e4 - (long)o * din);
             const float go = gs * dz[l][o];
             float4 p = s4[e4];
-            p.x = hs_adam(p.x, go * acts[l][k], mm[q].x, vv[q].x, lr_bc1, rsqrt_bc2, b1, b2, eps);
-            p.y = hs_adam(p.y, go * acts[l][k + 1], mm[q].y, vv[q].y, lr_bc1, rsqrt_bc2, b1, b2, eps);
-            p.z = hs_adam(p.z, go * acts[l][k + 2], mm[q].z, vv[q].z, lr_bc1, rsqrt_bc2, b1, b2, eps);
-            p.w = hs_adam(p.w, go * acts[l][k + 3], mm[q].w, vv[q].w, lr_bc1, rsqrt_bc2, b1, b2, eps);
+            p.x = hs_adam(p.x, go * acts[l][k], mm[q].x, vv[q].x, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+            p.y = hs_adam(p.y, go * acts[l][k + 1], mm[q].y, vv[q].y, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+            p.z = hs_adam(p.z, go * acts[l][k + 2], mm[q].z, vv[q].z, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+            p.w = hs_adam(p.w, go * acts[l][k + 3], mm[q].w, vv[q].w, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
             m4[e4] = mm[q];
             v4[e4] = vv[q];
             A4[e4] = p;
@@ -522,7 +534,7 @@ __global__ void __launch_bounds__(HS_NT) k_hyper_small(float* __restrict__ A, fl
         const int o = (int)(e / din), k = (int)(e - (long)o * din);
         const long ge = d.w[l] + e;
         float mm = m[ge], vv = v[ge];
-        const float p = hs_adam(sm[ow + e], gs * dz[l][o] * acts[l][k], mm, vv, lr_bc1, rsqrt_bc2, b1, b2, eps);
+        const float p = hs_adam(sm[ow + e], gs * dz[l][o] * acts[l][k], mm, vv, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
         m[ge] = mm;
         v[ge] = vv;
         A[ge] = p;
@@ -532,7 +544,7 @@ __global__ void __launch_bounds__(HS_NT) k_hyper_small(float* __restrict__ A, fl
       for (int o = tid; o < H; o += HS_NT) {
         const long ge = d.b[l] + o;
         float mm = m[ge], vv = v[ge];
-        const float p = hs_adam(sm[ob + o], gs * dz[l][o], mm, vv, lr_bc1, rsqrt_bc2, b1, b2, eps);
+        const float p = hs_adam(sm[ob + o], gs * dz[l][o], mm, vv, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
         m[ge] = mm;
         v[ge] = vv;
         A[ge] = p;
@@ -567,8 +579,9 @@ __global__ void __launch_bounds__(HR4_NT) k_hyper_adam_rows4(float* __restrict__
                                                              const float* __restrict__ f_n,
                                                              const float* __restrict__ u_n,
                                                              float* __restrict__ delta_n, float* __restrict__ partial,
-                                                             long P, int H, float lr_bc1, float rsqrt_bc2, float b1,
-                                                             float b2, float eps, const int* __restrict__ enable) {
+                                                             long P, int H, float lr_bc1, float rsqrt_bc2, float c1,
+                                                             float b2, float c2, float eps,
+                                                             const int* __restrict__ enable) {
   if (enable != nullptr && *enable == 0) return;
   __shared__ float red[HR4_NT / 64][HR_HMAX];
   __shared__ float sq[HR4_NT / 64];
@@ -604,10 +617,10 @@ __global__ void __launch_bounds__(HR4_NT) k_hyper_adam_rows4(float* __restrict__
       if (!act) w[q] = make_float4(0.f, 0.f, 0.f, 0.f);
       const float dr = gs * delta_k[rr];
       {  // head Adam on this lane's 4 columns (k_hyper_adam_v)
-        w[q].x = hs_adam(w[q].x, dr * fk.x, mm[q].x, vv[q].x, lr_bc1, rsqrt_bc2, b1, b2, eps);
-        w[q].y = hs_adam(w[q].y, dr * fk.y, mm[q].y, vv[q].y, lr_bc1, rsqrt_bc2, b1, b2, eps);
-        w[q].z = hs_adam(w[q].z, dr * fk.z, mm[q].z, vv[q].z, lr_bc1, rsqrt_bc2, b1, b2, eps);
-        w[q].w = hs_adam(w[q].w, dr * fk.w, mm[q].w, vv[q].w, lr_bc1, rsqrt_bc2, b1, b2, eps);
+        w[q].x = hs_adam(w[q].x, dr * fk.x, mm[q].x, vv[q].x, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+        w[q].y = hs_adam(w[q].y, dr * fk.y, mm[q].y, vv[q].y, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+        w[q].z = hs_adam(w[q].z, dr * fk.z, mm[q].z, vv[q].z, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+        w[q].w = hs_adam(w[q].w, dr * fk.w, mm[q].w, vv[q].w, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
         if (act && rv) {
           W4[r * H4 + j] = w[q];
           m4[r * H4 + j] = mm[q];
@@ -616,7 +629,7 @@ __global__ void __launch_bounds__(HR4_NT) k_hyper_adam_rows4(float* __restrict__
       }
       // bias Adam (every lane of the half computes it, lane 0 stores)
       float bm = m[nW + rr], bv = v[nW + rr];
-      const float bn = hs_adam(b[rr], dr, bm, bv, lr_bc1, rsqrt_bc2, b1, b2, eps);
+      const float bn = hs_adam(b[rr], dr, bm, bv, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
       // client k+1's rows pass on the updated row
       float d = w[q].x * fn.x + w[q].y * fn.y + w[q].z * fn.z + w[q].w * fn.w;
 #pragma unroll
@@ -668,8 +681,8 @@ __global__ void __launch_bounds__(HR4_NT) k_hyper_adam_rows4(float* __restrict__
 __global__ void __launch_bounds__(256) k_hyper_adam_v(float* __restrict__ W, float* __restrict__ bvec,
                                                       float* __restrict__ m, float* __restrict__ v,
                                                       const float* __restrict__ delta, const float* __restrict__ f,
-                                                      long P, int H, float lr_bc1, float rsqrt_bc2, float b1,
-                                                      float b2, float eps, const float* __restrict__ gsp,
+                                                      long P, int H, float lr_bc1, float rsqrt_bc2, float c1,
+                                                      float b2, float c2, float eps, const float* __restrict__ gsp,
                                                       const int* __restrict__ enable) {
   if (enable != nullptr && *enable == 0) return;
   __shared__ float fs[HS_HMAX];
@@ -687,10 +700,10 @@ __global__ void __launch_bounds__(256) k_hyper_adam_v(float* __restrict__ W, flo
     const int h = (int)(e - r * H);
     const float dr = gs * delta[r];
     float4 p = W4[i], mm = m4[i], vv = v4[i];
-    p.x = hs_adam(p.x, dr * fs[h], mm.x, vv.x, lr_bc1, rsqrt_bc2, b1, b2, eps);
-    p.y = hs_adam(p.y, dr * fs[h + 1], mm.y, vv.y, lr_bc1, rsqrt_bc2, b1, b2, eps);
-    p.z = hs_adam(p.z, dr * fs[h + 2], mm.z, vv.z, lr_bc1, rsqrt_bc2, b1, b2, eps);
-    p.w = hs_adam(p.w, dr * fs[h + 3], mm.w, vv.w, lr_bc1, rsqrt_bc2, b1, b2, eps);
+    p.x = hs_adam(p.x, dr * fs[h], mm.x, vv.x, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+    p.y = hs_adam(p.y, dr * fs[h + 1], mm.y, vv.y, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+    p.z = hs_adam(p.z, dr * fs[h + 2], mm.z, vv.z, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+    p.w = hs_adam(p.w, dr * fs[h + 3], mm.w, vv.w, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
     W4[i] = p;
     m4[i] = mm;
     v4[i] = vv;
@@ -700,7 +713,7 @@ __global__ void __launch_bounds__(256) k_hyper_adam_v(float* __restrict__ W, flo
     const float g = gs * delta[r];
     const long e = nW + r;
     float mi = m[e], vi = v[e];
-    bvec[r] = hs_adam(bvec[r], g, mi, vi, lr_bc1, rsqrt_bc2, b1, b2, eps);
+    bvec[r] = hs_adam(bvec[r], g, mi, vi, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
     m[e] = mi;
     v[e] = vi;
   }
@@ -721,7 +734,7 @@ __global__ void __launch_bounds__(HR4_NT) k_hyper_gen4(float* __restrict__ W, fl
                                                        const float* __restrict__ f_k, const float* __restrict__ gsp,
                                                        const float* __restrict__ gfeat, int ngen,
                                                        float* __restrict__ out, long P, int H, float lr_bc1,
-                                                       float rsqrt_bc2, float b1, float b2, float eps,
+                                                       float rsqrt_bc2, float c1, float b2, float c2, float eps,
                                                        const int* __restrict__ enable) {
   __shared__ float4 fs[HG_MAXC][HR_HMAX / 4];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -770,17 +783,17 @@ __global__ void __launch_bounds__(HR4_NT) k_hyper_gen4(float* __restrict__ W, fl
       if (upd) {
         const float dr = gs * delta_k[rr];
         // head Adam on this lane's 4 columns (k_hyper_adam_v's arithmetic)
-        w[q].x = hs_adam(w[q].x, dr * fk.x, mm[q].x, vv[q].x, lr_bc1, rsqrt_bc2, b1, b2, eps);
-        w[q].y = hs_adam(w[q].y, dr * fk.y, mm[q].y, vv[q].y, lr_bc1, rsqrt_bc2, b1, b2, eps);
-        w[q].z = hs_adam(w[q].z, dr * fk.z, mm[q].z, vv[q].z, lr_bc1, rsqrt_bc2, b1, b2, eps);
-        w[q].w = hs_adam(w[q].w, dr * fk.w, mm[q].w, vv[q].w, lr_bc1, rsqrt_bc2, b1, b2, eps);
+        w[q].x = hs_adam(w[q].x, dr * fk.x, mm[q].x, vv[q].x, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+        w[q].y = hs_adam(w[q].y, dr * fk.y, mm[q].y, vv[q].y, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+        w[q].z = hs_adam(w[q].z, dr * fk.z, mm[q].z, vv[q].z, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
+        w[q].w = hs_adam(w[q].w, dr * fk.w, mm[q].w, vv[q].w, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
         if (act && rv) {
           W4[r * H4 + j] = w[q];
           m4[r * H4 + j] = mm[q];
           v4[r * H4 + j] = vv[q];
         }
         float bm = m[nW + rr], bvv = v[nW + rr];
-        bn = hs_adam(b[rr], dr, bm, bvv, lr_bc1, rsqrt_bc2, b1, b2, eps);
+        bn = hs_adam(b[rr], dr, bm, bvv, lr_bc1, rsqrt_bc2, c1, b2, c2, eps);
         if (rv && j == 0) {
           m[nW + r] = bm;
           v[nW + r] = bvv;
@@ -832,7 +845,7 @@ void afl_hyper_generate(const float* A, const HySmallDesc& d, long offW, long of
     const int m = n - c0 < HG_MAXC ? n - c0 : HG_MAXC;
     hipLaunchKernelGGL(k_hyper_gen4<false>, dim3(nb), dim3(HR4_NT), 0, s, W, bv, nullptr, nullptr, nullptr, nullptr,
                        nullptr, feat + (long)c0 * d.H, m, out + (long)c0 * P, P, d.H, 0.f, 0.f, 0.f, 0.f, 0.f,
-                       nullptr);
+                       0.f, nullptr);
   }
 }
 
@@ -844,7 +857,7 @@ static bool hs_flat_ok(const HySmallDesc& d, long nsmall) {
 
 void afl_hyper_server_update(float* A, float* m, float* v, const float* U, const long* urow, const int* clients,
                              int n, const HySmallDesc& d, long offW, long offB, long P, int step0, float lr,
-                             float clip, float b1, float b2, float eps, float* delta, float* partial, float* feat,
+                             float clip, double b1, double b2, float eps, float* delta, float* partial, float* feat,
                              float* info, const int* enable, const int* gen, int ngen, float* gen_feat,
                              float* gen_out, hipStream_t s) {
   // gen (optional, ngen <= HG_MAXC): the clients whose models the updated hypernetwork generates next; the last
@@ -858,7 +871,7 @@ void afl_hyper_server_update(float* A, float* m, float* v, const float* U, const
   const long nsmall = offW - d.emb;
   const auto small = hs_flat_ok(d, nsmall) ? k_hyper_small<true> : k_hyper_small<false>;
   hipLaunchKernelGGL(small, dim3(1), dim3(HS_NT), 0, s, A, m, v, partial, nb, -1, clients[0], feat, info, d,
-                     nsmall, clip, 0.f, 0.f, b1, b2, eps, enable, gl, 0, gen_feat);
+                     nsmall, clip, 0.f, 0.f, 0.f, 0.f, 0.f, eps, enable, gl, 0, gen_feat);  // (features only)
   const long nW4 = P * H / 4;
   const int nba = (int)min(4096L, (nW4 + 255) / 256);
   // the rows pass of client k + 1 rides in client k's head Adam (k_hyper_adam_rows4) when the heads are
@@ -870,8 +883,8 @@ void afl_hyper_server_update(float* A, float* m, float* v, const float* U, const
 #endif
   for (int k = 0; k < n; ++k) {
     const int step = step0 + k + 1;
-    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    const float lr_bc1 = (float)(lr / bc1), rbc2 = (float)(1.0 / sqrt(bc2));
+    const HyCoefs co = hy_coefs(lr, b1, b2, step);
+    const float lr_bc1 = co.lr_bc1, rbc2 = co.rbc2, c1 = co.c1, b2f = co.b2, c2 = co.c2;
     float* fk = feat + (k & 1) * HS_HMAX;
     float* fn = feat + ((k + 1) & 1) * HS_HMAX;
     float* dk = delta + (k & 1) * P;
@@ -886,18 +899,18 @@ void afl_hyper_server_update(float* A, float* m, float* v, const float* U, const
     }
     const bool last = k + 1 == n;
     hipLaunchKernelGGL(small, dim3(1), dim3(HS_NT), 0, s, A, m, v, partial, nb, clients[k],
-                       last ? -1 : clients[k + 1], fn, info + 2 * k, d, nsmall, clip, lr_bc1, rbc2, b1, b2, eps,
+                       last ? -1 : clients[k + 1], fn, info + 2 * k, d, nsmall, clip, lr_bc1, rbc2, c1, b2f, c2, eps,
                        enable, gl, last ? ngen : 0, gen_feat);
     if (fused && !last)
       hipLaunchKernelGGL(k_hyper_adam_rows4, dim3(nb), dim3(HR4_NT), 0, s, W, bv, m + offW, v + offW, dk, fk,
-                         info + 2 * k + 1, fn, U + urow[k + 1] * P, dn, partial, P, H, lr_bc1, rbc2, b1, b2, eps,
+                         info + 2 * k + 1, fn, U + urow[k + 1] * P, dn, partial, P, H, lr_bc1, rbc2, c1, b2f, c2, eps,
                          enable);
     else if (fused && ngen > 0)  // the last head Adam with the next generation in the same sweep
       hipLaunchKernelGGL(k_hyper_gen4<true>, dim3(nb), dim3(HR4_NT), 0, s, W, bv, m + offW, v + offW, dk, fk,
-                         info + 2 * k + 1, gen_feat, ngen, gen_out, P, H, lr_bc1, rbc2, b1, b2, eps, enable);
+                         info + 2 * k + 1, gen_feat, ngen, gen_out, P, H, lr_bc1, rbc2, c1, b2f, c2, eps, enable);
     else
       hipLaunchKernelGGL(k_hyper_adam_v, dim3(nba), dim3(256), 0, s, W, bv, m + offW, v + offW, dk, fk, P, H,
-                         lr_bc1, rbc2, b1, b2, eps, info + 2 * k + 1, enable);
+                         lr_bc1, rbc2, c1, b2f, c2, eps, info + 2 * k + 1, enable);
   }
   if (ngen > 0 && !fused) afl_hyper_generate(A, d, offW, offB, P, gen_feat, ngen, gen_out, s);
 }
