@@ -630,9 +630,12 @@ struct VecAd {
 //   elements [NA, N - NV)  the same m';                             v' = fma(g, (1 - b2) g, b2 v)
 //   elements [N - NV, N)   m' = fma(c1, g - keep m, keep m);        v' = fma(g, (1 - b2) g, b2 v)
 //   all                    p' = fma(-(lr_bc1 m'), 1 / fma(rsqrt_bc2, sqrt(v'), eps), p)
-// unit_adam is (16, 16, 0), smu_adam (12, 4, 0): its dense tile has the first form, its ffn.3 / ffn.0 tiles the
-// second; the last NV elements are a thread's vector entries, in the form their own pass (vec_adam, until it was
-// folded in here) had pinned for them.
+// The passes: unit_adam is (16 + NV, 16, NV) — the laggards' v unit with their vector entries (NV = 2), the leaders'
+// out_proj unit (NV = 0); ffn_adam, the leaders' ffn.3 / ffn.0 tiles before counter A, is (8, 0, 0): the second form;
+// dense_adam, the leaders' dense tile with their vector entries, is (6, 4, 2).  The last NV elements are a thread's
+// vector entries, in the form their own pass (vec_adam, until it was folded in here) had pinned for them.  (Until the
+// ffn tiles got a pass of their own, the three small tiles were one (14, 4, 2) pass: every element keeps the form it
+// had there.)
 template <int N, int NA, int NV>
 __device__ __forceinline__ void adam_pinned(float (&p)[N], float (&mm)[N], float (&vv)[N], const float (&g)[N],
                                             const AdamK& K) {
@@ -775,54 +778,69 @@ __device__ __forceinline__ void smu_elem(int s, int w4, int lane, int i, int& pi
     img = B_IMG_F1 + n * LD64 + pcol(k) * 2;
   }
 }
-// Adam on the 12 elements of a small unit (S = {m0 m1 m2, v0 v1 v2, p0 p1 p2}), gradients g[3], and on the thread's NV
-// vector entries in the same stages (unit_adam)
-template <int NV>
-__device__ __forceinline__ void smu_adam(f4v (&S)[9], const f4v (&gs)[3], const AdamK& K, VS (&pa)[NCMP], VecAd& x) {
-  static_assert(NV == 0 || NV == NCMP, "all of the thread's vector entries or none");
-  float p[12 + NV], mm[12 + NV], vv[12 + NV], g[12 + NV];
+// Adam on a leader's ffn.3 and ffn.0 tiles (F = {m1 m2, v1 v2, p1 p2}: small-unit slots 1, 2 / 4, 5 / 7, 8), gradients
+// g3 / g1: the pass the leaders run before counter A (br_update)
+__device__ __forceinline__ void ffn_adam(f4v (&F)[6], const f4v& g3, const f4v& g1, const AdamK& K) {
+  float p[8], mm[8], vv[8], g[8];
 #pragma unroll
-  for (int s = 0; s < 3; ++s)
+  for (int s = 0; s < 2; ++s)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      mm[4 * s + i] = S[s][i];
-      vv[4 * s + i] = S[3 + s][i];
-      p[4 * s + i] = S[6 + s][i];
-      g[4 * s + i] = gs[s][i];
+      mm[4 * s + i] = F[s][i];
+      vv[4 * s + i] = F[2 + s][i];
+      p[4 * s + i] = F[4 + s][i];
+      g[4 * s + i] = s == 0 ? g3[i] : g1[i];
     }
+  adam_pinned<8, 0, 0>(p, mm, vv, g, K);
 #pragma unroll
-  for (int h = 0; h < NV; ++h) {
-    mm[12 + h] = x.m[h];
-    vv[12 + h] = x.v[h];
-    p[12 + h] = ar(pa[h].p);
-    g[12 + h] = x.g[h];
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      F[s][i] = mm[4 * s + i];
+      F[2 + s][i] = vv[4 * s + i];
+      F[4 + s][i] = p[4 * s + i];
+    }
+}
+// Adam on a leader's dense tile (D = {m, v, p}: small-unit slots 0, 3, 6; gradient gd) and on the thread's vector
+// entries in the same stages (unit_adam)
+__device__ __forceinline__ void dense_adam(f4v (&D)[3], const f4v& gd, const AdamK& K, VS (&pa)[NCMP], VecAd& x) {
+  constexpr int N = 4 + NCMP;
+  float p[N], mm[N], vv[N], g[N];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    mm[i] = D[0][i];
+    vv[i] = D[1][i];
+    p[i] = D[2][i];
+    g[i] = gd[i];
   }
-  adam_pinned<12 + NV, 4, NV>(p, mm, vv, g, K);
 #pragma unroll
-  for (int s = 0; s < 3; ++s)
+  for (int h = 0; h < NCMP; ++h) {
+    mm[4 + h] = x.m[h];
+    vv[4 + h] = x.v[h];
+    p[4 + h] = ar(pa[h].p);
+    g[4 + h] = x.g[h];
+  }
+  adam_pinned<N, 4, NCMP>(p, mm, vv, g, K);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      S[s][i] = mm[4 * s + i];
-      S[3 + s][i] = vv[4 * s + i];
-      S[6 + s][i] = p[4 * s + i];
-    }
+  for (int i = 0; i < 4; ++i) {
+    D[0][i] = mm[i];
+    D[1][i] = vv[i];
+    D[2][i] = p[i];
+  }
 #pragma unroll
-  for (int h = 0; h < NV; ++h) {
-    x.m[h] = mm[12 + h];
-    x.v[h] = vv[12 + h];
-    x.pn[h] = p[12 + h];
-    pa[h].p = aw(p[12 + h]);
+  for (int h = 0; h < NCMP; ++h) {
+    x.m[h] = mm[4 + h];
+    x.v[h] = vv[4 + h];
+    x.pn[h] = p[4 + h];
+    pa[h].p = aw(p[4 + h]);
   }
 }
-// the small unit's new weights into the three images (4 consecutive (permuted) k per lane: one 8-byte store each)
+// the new weights p of small tile s into its image (4 consecutive (permuted) k per lane: one 8-byte store)
 template <int BR>
-__device__ __forceinline__ void smu_img(uchar* smem, const f4v (&S)[9], int w4, int lane) {
-#pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    int pi, img;
-    smu_elem<BR>(s, w4, lane, 0, pi, img);
-    *(LDS_AS u32x2v*)(smem + img) = u32x2v{pk2(S[6 + s][0], S[6 + s][1]), pk2(S[6 + s][2], S[6 + s][3])};
-  }
+__device__ __forceinline__ void smu_img(uchar* smem, int s, const f4v& p, int w4, int lane) {
+  int pi, img;
+  smu_elem<BR>(s, w4, lane, 0, pi, img);
+  *(LDS_AS u32x2v*)(smem + img) = u32x2v{pk2(p[0], p[1]), pk2(p[2], p[3])};
 }
 
 // Weight gradients + Adam for one step, started by each wave as soon as its own backward is done — no barrier
@@ -831,24 +849,32 @@ __device__ __forceinline__ void smu_img(uchar* smem, const f4v (&S)[9], int w4, 
 // step's critical path).  Each wave starts what its inputs allow, tracked by progress counters (every wave signals
 // them from its backward):
 //   leaders   counter C (every wave's ffn.3 / ffn.0 dY rows): the ffn.3 tile w4 and ffn.0 k tile w4 weight
-//             gradients and the ffn.3 / ffn.0 bias sums — work that used to follow the barrier, now done while
-//             the laggards are still in their backward; then counter A (every wave's out_proj dY rows, the
-//             out_proj image no longer read): their out_proj unit — dW over the 128 rows, Adam on the workspace
-//             copy (p, m, v), image, bias sums; then counter B (every wave's dense dY rows): the dense tile w4
-//             and its bias sums;
+//             gradients and the ffn.3 / ffn.0 bias sums, then — still before A, at priority 0 — the abort decision,
+//             Adam on those two tiles (ffn_adam), their images and their workspace stores: work that used to follow
+//             the barrier, then counter A, now done while the laggards are still in their backward; then counter A
+//             (every wave's out_proj dY rows, the out_proj image no longer read): their out_proj unit — dW over the
+//             128 rows, Adam on the workspace copy (p, m, v), image, bias sums; then counter B (every wave's dense dY
+//             rows): the dense tile w4 and its bias sums, and Adam on that tile (dense_adam), its image and stores;
 //   laggards  counter A (the v unit's dY rows): their in_proj.v unit, whose new bf16 weights wait for counter B (the
 //             v image is read until the end of every wave's backward).
-// The leaders then run Adam on their small unit (the dense / ffn.3 / ffn.0 tiles, workspace-resident like the
-// blocks) and write its images — in their slack while the laggards finish the v block.  Inside those Adam passes
-// (laggards: the v unit's, leaders: the small unit's) every wave also runs Adam on the vector entries it owns (the
-// 648 bias / LayerNorm elements, at most 2 per thread, profiles/ab_tf2_frag_pipeline.log): an entry belongs to the
-// thread whose registers hold its gradient sum — a column of one of the wave's all-ones MFMA accumulators, or the
-// LayerNorm accumulator the thread reads (vec_entry) — so nothing is staged through LDS and the only barrier after
-// the units is the step's end barrier.  (Before, the sums went to an fp32 staging array behind one barrier and
-// were read back by thread e % 512 behind a second: 0.8 us of every wave's step; and 5 entries per thread when the
-// small weights were vector entries too: +3.6 %, profiles/ab_tf2_r6_update.log.)  The abort decision (a NaN loss
-// anywhere in the batch) is taken by every wave after counter A — every abort word is written before its wave
-// signals — before anything is updated.  Returns false on abort.
+// The small unit (the dense / ffn.3 / ffn.0 tiles of a leader) is workspace-resident like the blocks.  Its ffn tiles
+// are updated before A because nothing they need comes later: their gradients are complete ~0.4 us after C, and C
+// also frees their images (ffn.3^T is read in br_bwd_pre, ffn.0^T before each wave's C signal).  Behind A, as part of
+// one 14-element pass with the dense tile, they were 8 sqrt -> rcp -> fma chains, two image writes and six stores of
+// the leaders' post-A tail, at priority 2 on the SIMD the critical laggard needs: +2.2 % rounds/s for moving them
+// (profiles/ab_tf2_update_tail.log; also there, rejected: one Adam pass for out_proj + dense + vector entries after
+// B, -0.4 % alone, and the laggards' abort read joined with unit_dw's first fragment reads, inside the noise).
+// Inside the last Adam pass of each role (laggards: the v unit's, leaders: the dense tile's) every wave also runs Adam
+// on the vector entries it owns (the 648 bias / LayerNorm elements, at most 2 per thread,
+// profiles/ab_tf2_frag_pipeline.log): an entry belongs to the thread whose registers hold its gradient sum — a column
+// of one of the wave's all-ones MFMA accumulators, or the LayerNorm accumulator the thread reads (vec_entry) — so
+// nothing is staged through LDS and the only barrier after the units is the step's end barrier.  (Before, the sums
+// went to an fp32 staging array behind one barrier and were read back by thread e % 512 behind a second: 0.8 us of
+// every wave's step; and 5 entries per thread when the small weights were vector entries too: +3.6 %,
+// profiles/ab_tf2_r6_update.log.)  The abort decision (a NaN loss anywhere in the batch) is taken by every wave before
+// it updates anything: by the laggards after counter A, by the leaders after counter C already — all eight abort words
+// are final once every wave has passed C, because a wave writes its word before br_backward and its C signal drains
+// its LDS operations (the time-out path writes the word before it signals).  Returns false on abort.
 // (Measured first: the leaders taking both units after counter A was 1 % slower — A is reached only ~0.2 us
 // before B, so the leaders' two units became the tail; profiles/ab_tf2_r6_update.log.)
 template <int BR>
@@ -873,59 +899,35 @@ __device__ __forceinline__ bool br_update(uchar* smem, BrState& st, const AdamK&
   uint32_t o1 = 0x3F803F80u;  // (all-ones operand, opaque SGPR: see unit_dw)
   asm volatile("" : "+s"(o1));
   const s8v one = __builtin_bit_cast(s8v, u32x4{o1, o1, o1, o1});
-  if (lead) {
-    // the leaders' ffn tiles run below the laggards' backward on the same SIMD (priority 0: +1.9 % against 2,
-    // +1.7 % at 1; profiles/ab_tf2_r6_update.log), the out_proj unit after A at the critical priority again
-    prio_lo();
-    if (!lds_wait(smem, B_CNT_C, all)) {
-      if (lane == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return false;
-    }
-#pragma unroll  // (fully unrolled: the fragment reads of later k-steps overlap earlier MFMAs, +2.2 %)
-    for (int s = 0; s < (ABL(K, ABL_U1) ? 0 : 4); ++s) {
-      const s8v y3 = tfrag<TK64>(smem + B_DF3, 32 * s, w4, lane), y1 = tfrag<TK16>(smem + B_DF0, 32 * s, 0, lane);
-      a3 = mma(tfrag<TK16>(smem + B_F2, 32 * s, 0, lane), y3, a3);
-      af1 = mma(tfrag<TK64>(smem + B_X1N, 32 * s, w4, lane), y1, af1);
-      b3 = mma(one, y3, b3);
-      if (wave == 0) b1 = mma(one, y1, b1);
-    }
-    if (!lds_wait(smem, B_CNT_A, all)) {
-      if (lane == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return false;
-    }
-    prio_hi();
-  } else {
-    // (the v unit's operands are complete at A — only its image write waits for B, the end of every wave's
-    // backward — so the laggards' weight-gradient MFMAs overlap the last laggard's v backward)
-    if (!lds_wait(smem, B_CNT_A, all)) {
-      if (lane == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return false;
-    }
-  }
-  {
-    uint32_t any = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) any |= abort_w[i];
-    if (any) return false;
-  }
-  stp(4, tid);
+  auto timed_out = [&]() {
+    if (lane == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return false;
+  };
+  // the abort decision: the OR of the eight waves' abort words (two 16-byte reads, one LDS round trip)
+  auto abort_now = [&]() {
+    const u32x4 a = *(const LDS_AS u32x4*)abort_w, b = *(const LDS_AS u32x4*)(abort_w + 4);
+    const u32x4 o = a | b;
+    return (o[0] | o[1] | o[2] | o[3]) != 0;
+  };
   // ---- the vector entries (648 bias / LayerNorm elements), owner-computed: every gradient sum ends in a register of
   // the thread that owns the entry (vec_entry) — the bias sums in the all-ones MFMA accumulators, the LayerNorm sums
-  // read here from the fp64 accumulators.  Those are complete at counter A, which this wave has passed: every
+  // read (vec_g0) from the fp64 accumulators.  Those are complete at counter A, which the wave has passed then: every
   // ln_colsum of br_backward precedes its wave's lds_signal(B_CNT_A), and the signal drains the wave's LDS operations
-  // first; the backward's last VEC read (gamma1) precedes that signal too, so from here on an owner may write its VEC
-  // words.  The slot is zeroed by its reader and added to again only after the step's end barrier.  The entries'
-  // Adam rides in the stages of a unit's Adam (laggards: unit_adam, whose v bias sums exist after unit_dw; leaders:
-  // smu_adam, right after their last input, the dense bias sums) as two more independent chains, and each owner
-  // writes its VEC words next to the unit's image: no staging, no barrier, no dependent chain of its own at the end
-  // of the step (it cost every wave ~0.4 us there).  Threads without an entry compute on zeros and store nothing.
+  // first; the backward's last VEC read (gamma1) precedes that signal too, so from there on an owner may write its VEC
+  // words.  The slot is zeroed by its reader and added to again only after the step's end barrier.  The entries' Adam
+  // rides in the stages of a unit's Adam (laggards: unit_adam, whose v bias sums exist after unit_dw; leaders:
+  // dense_adam, right after their last input, the dense bias sums) as two more independent chains, and each owner
+  // writes its VEC words next to the unit's image: no staging, no barrier, no dependent chain of its own at the end of
+  // the step (it cost every wave ~0.4 us there).  Threads without an entry compute on zeros and store nothing.
   VecAd x;
-  x.g[0] = b1[0];
-  if (wave >= 2) {
-    LDS_AS double* q = (LDS_AS double*)(smem + B_DBL) + 64 * (wave - 2) + lane;
-    x.g[0] = lds_getq(smem + B_DBL, 64 * (wave - 2) + lane);
-    *q = 0.0;
-  }
+  auto vec_g0 = [&]() {  // (after counter A and the abort decision)
+    x.g[0] = b1[0];
+    if (wave >= 2) {
+      LDS_AS double* q = (LDS_AS double*)(smem + B_DBL) + 64 * (wave - 2) + lane;
+      x.g[0] = lds_getq(smem + B_DBL, 64 * (wave - 2) + lane);
+      *q = 0.0;
+    }
+  };
   auto vec_in = [&]() {  // (once the wave's bias sums exist)
     x.g[1] = g == 0 ? bsu[0][0] : g == 1 ? bsu[1][0] : g == 2 ? b3[0] : bd[0];
     x.m[0] = cmom[0], x.m[1] = cmom[1], x.v[0] = cmom[2], x.v[1] = cmom[3];
@@ -939,53 +941,87 @@ __device__ __forceinline__ bool br_update(uchar* smem, BrState& st, const AdamK&
       if (vec_real(e)) ldsf(smem, B_VEC)[e] = x.pn[h];
     }
   };
-  {  // the unit: out_proj (leaders: X = a, dY = d o) or in_proj.v (laggards: X = h0, dY = d v)
-    f4v acc[2][2];
-    if (!ABL(K, ABL_UDW))
-      unit_dw(smem + (lead ? B_A : B_H0), smem + (lead ? B_DO : B_DV), Ta, Tb, lane, do_bias, acc, bsu);
-    if (!lead) {
-      vec_in();
-      if (!ABL(K, ABL_UADAM)) unit_adam<NCMP>(U, acc, K, st.cmp, x);
-    } else {
-      if (!ABL(K, ABL_UADAM)) unit_adam<0>(U, acc, K, st.cmp, x);
-    }
-    u32x2v w[4];
+  f4v acc[2][2];
+  u32x2v w[4];
+  if (!lead) {
+    // ---- the laggards: the in_proj.v unit (X = h0, dY = d v).  Its operands are complete at A — only its image write
+    // waits for B, the end of every wave's backward — so its weight-gradient MFMAs overlap the last laggard's v backward
+    if (!lds_wait(smem, B_CNT_A, all)) return timed_out();
+    if (abort_now()) return false;
+    stp(4, tid);
+    vec_g0();
+    if (!ABL(K, ABL_UDW)) unit_dw(smem + B_H0, smem + B_DV, Ta, Tb, lane, do_bias, acc, bsu);
+    vec_in();
+    if (!ABL(K, ABL_UADAM)) unit_adam<NCMP>(U, acc, K, st.cmp, x);
     unit_pack(U, w);
-    if (!lead && !lds_wait(smem, B_CNT_B, all)) {  // (the v image is read until the end of every wave's backward)
-      if (lane == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return false;
-    }
-    unit_img(smem, B::vo(!lead), Ta, Tb, lane, w);
-    if (!lead && !ABL(K, ABL_UADAM)) vec_out();
+    // (the v image is read until the end of every wave's backward)
+    if (!lds_wait(smem, B_CNT_B, all)) return timed_out();
+    unit_img(smem, B::vo(true), Ta, Tb, lane, w);
+    if (!ABL(K, ABL_UADAM)) vec_out();
 #pragma unroll
     for (int j = 0; j < 12; ++j) unit_st(rm, ui, j, lane, U[j]);
-    if (!lead) mom_st(rm, 0, tid, f4v{x.m[0], x.m[1], x.v[0], x.v[1]});
-  }
-  if (lead) {
-    f4v S[9];  // the small unit (issued here: its loads overlap the wait for B and the dense MFMAs)
-#pragma unroll
-    for (int j = 0; j < 9; ++j) S[j] = smu_ld(rm, w4, j, lane);
-    if (!lds_wait(smem, B_CNT_B, all)) {  // (the dense dY rows are complete at B)
-      if (lane == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return false;
-    }
-#pragma unroll  // (fully unrolled: the fragment reads of later k-steps overlap earlier MFMAs, +2.2 %)
-    for (int s = 0; s < (ABL(K, ABL_U1) ? 0 : 4); ++s) {
-      const s8v yd = tfrag<TK64>(smem + B_DZ0, 32 * s, w4, lane);
-      as = mma(tfrag<TK16>(smem + B_XIN, 32 * s, 0, lane), yd, as);
-      bd = mma(one, yd, bd);
-    }
-    // Adam on the small unit (dense, ffn.3, ffn.0 tiles); their images are free: the dense one is read only by the
-    // forward, the ffn ones by the backward before counters C / A
-    const f4v gs3[3] = {as, a3, af1};
-    vec_in();
-    if (!ABL(K, ABL_U3)) smu_adam<NCMP>(S, gs3, K, st.cmp, x);
-    smu_img<BR>(smem, S, w4, lane);
-    if (!ABL(K, ABL_U3)) vec_out();
-#pragma unroll
-    for (int j = 0; j < 9; ++j) smu_st(rm, w4, j, lane, S[j]);
     mom_st(rm, 0, tid, f4v{x.m[0], x.m[1], x.v[0], x.v[1]});
+    return true;
   }
+  // ---- the leaders.  Their ffn tiles and the Adam of those run below the laggards' backward on the same SIMD (priority
+  // 0: +1.9 % against 2, +1.7 % at 1; profiles/ab_tf2_r6_update.log), the out_proj unit after A at the critical
+  // priority again
+  prio_lo();
+  f4v F[6];  // the ffn.3 / ffn.0 slots of the small unit (in flight over the wait for C and the MFMAs, dead at A)
+#pragma unroll
+  for (int j = 0; j < 6; ++j) F[j] = smu_ld(rm, w4, 3 * (j >> 1) + 1 + (j & 1), lane);
+  if (!lds_wait(smem, B_CNT_C, all)) return timed_out();
+#pragma unroll  // (fully unrolled: the fragment reads of later k-steps overlap earlier MFMAs, +2.2 %)
+  for (int s = 0; s < (ABL(K, ABL_U1) ? 0 : 4); ++s) {
+    const s8v y3 = tfrag<TK64>(smem + B_DF3, 32 * s, w4, lane), y1 = tfrag<TK16>(smem + B_DF0, 32 * s, 0, lane);
+    a3 = mma(tfrag<TK16>(smem + B_F2, 32 * s, 0, lane), y3, a3);
+    af1 = mma(tfrag<TK64>(smem + B_X1N, 32 * s, w4, lane), y1, af1);
+    b3 = mma(one, y3, b3);
+    if (wave == 0) b1 = mma(one, y1, b1);
+  }
+  // The abort decision, before anything is written: all eight words are final once every wave has passed C (a wave
+  // writes its word before br_backward, and its C signal drains its LDS operations; the time-out path writes the word
+  // before it signals), so the leaders need not wait for A to take it.
+  if (abort_now()) return false;
+  // Adam on the ffn.3 / ffn.0 tiles, their images and their stores, here and not behind A: the gradients are complete,
+  // and from C on nobody reads the two images (ffn.3^T is read in br_bwd_pre, ffn.0^T before each wave's C signal, the
+  // forward's reads ended long before) — so this runs in the leaders' wait for A, at priority 0, instead of on the
+  // laggards' SIMDs in the step's tail.
+  if (!ABL(K, ABL_U3)) ffn_adam(F, a3, af1, K);
+  smu_img<BR>(smem, 1, F[4], w4, lane);
+  smu_img<BR>(smem, 2, F[5], w4, lane);
+#pragma unroll
+  for (int j = 0; j < 6; ++j) smu_st(rm, w4, 3 * (j >> 1) + 1 + (j & 1), lane, F[j]);
+  if (!lds_wait(smem, B_CNT_A, all)) return timed_out();
+  prio_hi();
+  stp(4, tid);
+  vec_g0();
+  // the out_proj unit (X = a, dY = d o): its image is free since A
+  if (!ABL(K, ABL_UDW)) unit_dw(smem + B_A, smem + B_DO, Ta, Tb, lane, do_bias, acc, bsu);
+  if (!ABL(K, ABL_UADAM)) unit_adam<0>(U, acc, K, st.cmp, x);
+  unit_pack(U, w);
+  unit_img(smem, B::vo(false), Ta, Tb, lane, w);
+#pragma unroll
+  for (int j = 0; j < 12; ++j) unit_st(rm, ui, j, lane, U[j]);
+  // the dense tile (its dY rows are complete at B); its slots' loads overlap the wait for B and the MFMAs.  Its image
+  // is free: it is read only by the forward.
+  f4v D[3];
+#pragma unroll
+  for (int s = 0; s < 3; ++s) D[s] = smu_ld(rm, w4, 3 * s, lane);
+  if (!lds_wait(smem, B_CNT_B, all)) return timed_out();
+#pragma unroll  // (fully unrolled: the fragment reads of later k-steps overlap earlier MFMAs, +2.2 %)
+  for (int s = 0; s < (ABL(K, ABL_U1) ? 0 : 4); ++s) {
+    const s8v yd = tfrag<TK64>(smem + B_DZ0, 32 * s, w4, lane);
+    as = mma(tfrag<TK16>(smem + B_XIN, 32 * s, 0, lane), yd, as);
+    bd = mma(one, yd, bd);
+  }
+  vec_in();
+  if (!ABL(K, ABL_U3)) dense_adam(D, as, K, st.cmp, x);
+  smu_img<BR>(smem, 0, D[2], w4, lane);
+  if (!ABL(K, ABL_U3)) vec_out();
+#pragma unroll
+  for (int s = 0; s < 3; ++s) smu_st(rm, w4, 3 * s, lane, D[s]);
+  mom_st(rm, 0, tid, f4v{x.m[0], x.m[1], x.v[0], x.v[1]});
   return true;
 }
 
@@ -1028,7 +1064,8 @@ __device__ __forceinline__ void br_init(uchar* smem, BrState& st, const float* P
         S[6 + s][i] = pi >= 0 ? P[pi] : 0.f;
       }
     }
-    smu_img<BR>(smem, S, wave, lane);
+#pragma unroll
+    for (int s = 0; s < 3; ++s) smu_img<BR>(smem, s, S[6 + s], wave, lane);
 #pragma unroll
     for (int j = 0; j < 9; ++j) smu_st(rm, wave, j, lane, S[j]);
   }

@@ -29,8 +29,8 @@ NAMES = {0: "F:G1 dense+E1", 1: "F:G2 vproj+E2", 2: "F:G3 oproj+E3 LN1", 3: "F:G
 # Head stamps of a critical wave (0-3); an importer wave (4-7) stamps 10 = wait for its half's critical waves,
 # 11 = import of the partner's rows.
 NAMES4 = {0: "B:forward", 1: "B:publish+prefetch+masks+backward prologue", 2: "B:wait d(out)", 3: "B:backward",
-          4: "B:leaders ffn tiles + wait counter A / laggards wait counter A, abort",
-          5: "B:units with the vector Adam in their stages (leaders out_proj + dense + small-unit Adam / laggards in_proj.v)",
+          4: "B:leaders ffn tiles, abort, ffn Adam + images + stores, wait counter A / laggards wait counter A",
+          5: "B:units with the vector Adam in their stages (leaders out_proj + dense, one Adam pass / laggards abort, in_proj.v)",
           6: "B:end barrier", 10: "H:wait branches",
           11: "H:fwd+loss+bwd+publish+export", 12: "H:bar+loss", 13: "H:dW+Adam", 14: "H:end barrier"}
 
