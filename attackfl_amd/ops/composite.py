@@ -76,7 +76,12 @@ def segment_l2_sum(diffs: torch.Tensor, slots) -> torch.Tensor:
 
 
 def batched_spectral_norm(mats: torch.Tensor) -> torch.Tensor:
-    return torch.linalg.matrix_norm(mats.double(), ord=2).to(torch.float64)
+    """[..., r, c] -> [...] fp64 ord-2 norms; NaN for exactly the matrices that hold a non-finite entry (LAPACK
+    refuses those), so a poisoned model is at distance NaN, which every bisection comparison rejects."""
+    m = mats.double()
+    bad = ~torch.isfinite(m).flatten(-2).all(dim=-1)
+    val = torch.linalg.matrix_norm(m.masked_fill(bad[..., None, None], 0.0), ord=2).to(torch.float64)
+    return val.masked_fill(bad, float("nan"))
 
 
 def attack_coeffs(G: torch.Tensor, mean: torch.Tensor, dev: torch.Tensor):

@@ -449,7 +449,15 @@ torch::Tensor spectral_norm(torch::Tensor X) {
   const int n = r <= c ? r : c;
   if (n > 128) {
     // rare (no model tensor has both dims > 128): exact batched SVD through the library
-    return at::linalg_matrix_norm(X.to(torch::kFloat64), 2).contiguous();
+    // (the solver refuses non-finite input and need not converge on a zero matrix: those go in as diag(1..n) and come
+    // out NaN, as from the kernels below, and 0; no host read)
+    auto Xd = X.to(torch::kFloat64);
+    auto flat = Xd.flatten(1);
+    auto bad = at::isfinite(flat).all(1).logical_not();
+    auto skip = bad.logical_or(flat.eq(0).all(1));
+    auto sub = at::eye(r, c, Xd.options()) * at::arange(1, c + 1, Xd.options());
+    auto val = at::linalg_matrix_norm(at::where(skip.view({B, 1, 1}), sub, Xd), 2);
+    return val.masked_fill(skip, 0.0).masked_fill(bad, std::numeric_limits<double>::quiet_NaN()).contiguous();
   }
   auto scratch = torch::empty({(long)B * afl_spectral_scratch(r, c)}, X.options());
   TORCH_CHECK(afl_spectral(X.data_ptr<float>(), B, r, c, scratch.data_ptr<float>(), out.data_ptr<double>(), cur()) == 0,

@@ -7,6 +7,10 @@
 //   3. v = the column of A^(4096) with the largest norm (spans the top eigenspace, exact even for a
 //      repeated top eigenvalue), sigma^2 = Rayleigh quotient v^T G v / v^T v against the ORIGINAL
 //      Gram (kept in global scratch), accumulated in fp64.
+// Range: the image is prescaled by 2^-e, e the exponent of max|G|, before the first squaring (a power of two commutes
+// with the squarings, with 1/mx and with the fp32 rounding, so every in-range result keeps its bits); the result is
+// relative wherever the fp32 Gram is representable (sigma roughly in [1e-18, 1e18]), 0 below and NaN above.
+// Non-finite: a NaN or Inf entry, or a Gram that overflows fp32, gives NaN (never 0: a distance of 0 would accept).
 #include "common.h"
 #include "kernels.h"
 
@@ -29,6 +33,7 @@ __device__ __forceinline__ void spectral_one(const float* __restrict__ x, int r,
   const int tid = threadIdx.x;
 
   // ---- 1. Gram ----
+  float gm = 0.f;  // max|G| of this thread's entries; +Inf for a non-finite one (fmaxf alone would drop a NaN)
   for (int e = tid; e < n8 * n8; e += blockDim.x) {
     int i = e / n8, j = e % n8;
     float s = 0.f;
@@ -37,12 +42,29 @@ __device__ __forceinline__ void spectral_one(const float* __restrict__ x, int r,
         for (int t = 0; t < k; ++t) s += x[(long)i * c + t] * x[(long)j * c + t];
       else
         for (int t = 0; t < k; ++t) s += x[(long)t * c + i] * x[(long)t * c + j];
+      const float a = fabsf(s);
+      gm = fmaxf(gm, a <= 3.402823466e+38f ? a : __builtin_inff());
     }
     if (j >= i) {
       A[i * ld + j] = s;
       A[j * ld + i] = s;
       g0[i * n8 + j] = s;
       g0[j * n8 + i] = s;
+    }
+  }
+  gm = wave_max(gm);
+  if ((tid & 63) == 0) red[tid >> 6] = gm;
+  __syncthreads();
+  gm = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  if (!(gm <= 3.402823466e+38f)) {  // (block-uniform) a non-finite entry of x, or the fp32 Gram overflowed
+    if (tid == 0) *out = __builtin_nan("");
+    return;
+  }
+  if (gm > 0.f) {  // prescale the image by a power of two: max|A| in [1, 2), so no squaring under- or overflows
+    const int ex = ilogbf(gm);
+    for (int e = tid; e < n8 * n8; e += blockDim.x) {
+      int i = e / n8, j = e % n8;
+      A[i * ld + j] = ldexpf(A[i * ld + j], -ex);
     }
   }
   __syncthreads();
@@ -284,7 +306,8 @@ __device__ __forceinline__ double sg_block_max(double v, double* red) {
 // forms the K candidate distances at the current γ — row 0 is the candidate itself (A-7: distance 0), row j
 // the closed-form vector slots sqrt(max(A - 2γB + γ²C, 0)) summed over Sv slots, plus the Gram-form
 // spectral sums spec[(j - 1) S + s] of this launch — tests them (kind 0: max_j d_j < thr, Min-Max / Opt-Fang;
-// 1: sum_j d_j² < thr, Min-Sum; a NaN distance rejects, as the torch comparison does) and moves γ by ±step/2.
+// 1: sum_j d_j² < thr, Min-Sum; a NaN distance rejects, as the torch comparison does: a NaN vector coefficient gives
+// one, and so does a matrix slot that holds a non-finite value, which k_spec_eval reports as NaN) and moves γ by ±step/2.
 constexpr int BS_TRIED = 4, BS_ACC = 20, BS_WORDS = 40;
 __device__ void bisect_decide(const AflBisect& b, const double* spec, int S, int it, double step) {
   __shared__ double rs[4], rm[4];
@@ -298,7 +321,7 @@ __device__ void bisect_decide(const AflBisect& b, const double* spec, int S, int
     if (j > 0) {
       for (int v = 0; v < b.Sv; ++v) {
         const double q = (b.vA[(long)j * b.Sv + v] - 2.0 * g * b.vB[(long)j * b.Sv + v]) + g * g * b.vC[v];
-        d += sqrt(q > 0.0 ? q : 0.0);
+        d += sqrt(q < 0.0 ? 0.0 : q);  // (a NaN coefficient stays NaN, as through torch's clamp_min)
       }
       for (int v = 0; v < S; ++v)  // (written by the other workgroups of this launch: coherent loads)
         d += __builtin_bit_cast(double, __hip_atomic_load((const unsigned long long*)(spec + (long)(j - 1) * S + v),
@@ -360,8 +383,12 @@ __global__ void __launch_bounds__(256) k_spec_eval(const double* __restrict__ ar
   auto gram = [&](int e) -> double { return gamma ? (A[e] - g * Sg[e]) + (g * g) * C[e] : A[e]; };
   // ---- 1. G(γ), normalised, as the fp32 image
   double mx = 0.0;
-  for (int e = tid; e < n16 * n16; e += 256) mx = fmax(mx, fabs(gram(e)));
+  for (int e = tid; e < n16 * n16; e += 256) {
+    const double a = fabs(gram(e));
+    mx = fmax(mx, a <= 1.7976931348623157e308 ? a : __builtin_inf());  // (fmax alone would drop a NaN)
+  }
   mx = sg_block_max(mx, red);
+  const bool bad = !(mx <= 1.7976931348623157e308);  // a non-finite entry of X, dev or γ: NaN, never distance 0
   double inv = mx > 0.0 ? 1.0 / mx : 0.0;
   for (int e = tid; e < n16 * n16; e += 256) {
     const int i = e / n16, l = e - i * n16;
@@ -456,7 +483,7 @@ __global__ void __launch_bounds__(256) k_spec_eval(const double* __restrict__ ar
     const double nn = (dred[0][0] + dred[0][1]) + (dred[0][2] + dred[0][3]);
     const double dd = (dred[1][0] + dred[1][1]) + (dred[1][2] + dred[1][3]);
     const double lam = dd > 0.0 ? nn / dd : 0.0;
-    const double val = lam > 0.0 ? sqrt(lam) : 0.0;
+    const double val = bad ? __builtin_nan("") : lam > 0.0 ? sqrt(lam) : 0.0;
     if (!BIS) {
       out[(long)m * S + s] = val;
     } else {  // fan-in: publish (coherent store), count arrivals; the last workgroup decides this γ
