@@ -48,8 +48,22 @@ AflDrop drop(const c10::optional<torch::Tensor>& seeds, const c10::optional<torc
   return d;
 }
 
-AflHarLayerW layer_w(const std::vector<int64_t>& w) {
+// a parameter block [off, off + n) must lie inside one client's row of params [C, P]
+void inrow(int64_t off, int64_t n, int64_t P, const char* what) {
+  TORCH_CHECK(off >= 0 && n >= 0 && off <= P && n <= P - off, what, ": offset ", off, " + ", n, " floats is outside a ",
+              P, "-float parameter row");
+}
+// params [C, P] fp32 for C clients
+int64_t prow(const torch::Tensor& params, int64_t C) {
+  TORCH_CHECK(params.dim() == 2 && params.size(0) == C, "params must be [C, P] with one row per client");
+  return params.size(1);
+}
+
+AflHarLayerW layer_w(const std::vector<int64_t>& w, int64_t P) {
   TORCH_CHECK(w.size() == 12, "layer offsets: 12 entries");
+  // AflHarLayerW order: in_proj w b | out_proj w b | norm1 w b | linear1 w b | linear2 w b | norm2 w b
+  static const int64_t n[12] = {192 * 64, 192, 64 * 64, 64, 64, 64, 256 * 64, 256, 64 * 256, 64, 64, 64};
+  for (int i = 0; i < 12; ++i) inrow(w[i], n[i], P, "layer offset");
   return AflHarLayerW{(int)w[0], (int)w[1], (int)w[2], (int)w[3], (int)w[4],  (int)w[5],
                       (int)w[6], (int)w[7], (int)w[8], (int)w[9], (int)w[10], (int)w[11]};
 }
@@ -68,15 +82,20 @@ void har_stem(torch::Tensor x, torch::Tensor params, int64_t w_off, int64_t b_of
   TORCH_CHECK(x.dim() == 3, "x must be [C, B, L]");
   const int64_t C = x.size(0), B = x.size(1), L = x.size(2);
   rows64(h, C, B * L, "h");
+  const int64_t P = prow(params, C);
+  TORCH_CHECK(B >= 1 && L >= 1, "x must have B >= 1 and L >= 1");
+  inrow(w_off, 192, P, "conv weight");
+  inrow(b_off, 64, P, "conv bias");
+  inrow(pe_off, 64 * L, P, "positional encoding (64 L floats)");
   ok(afl_har_stem(xp, (int)C, (int)B, (int)L, f32(params, "params"), params.size(1), (int)w_off, (int)b_off, (int)pe_off,
                   bf(h, "h"), cur()),
      "har_stem");
 }
 
 void har_pool(torch::Tensor y, int64_t B, int64_t L, torch::Tensor out) {
+  TORCH_CHECK(out.dim() == 3 && out.size(1) == B && out.size(2) == 64 && B >= 1 && L >= 1, "out must be [C, B, 64]");
   const int64_t C = out.size(0);
   rows64(y, C, B * L, "y");
-  TORCH_CHECK(out.dim() == 3 && out.size(1) == B && out.size(2) == 64, "out must be [C, B, 64]");
   ok(afl_har_pool(bf(y, "y"), (int)C, (int)B, (int)L, f32(out, "out"), cur()), "har_pool");
 }
 
@@ -85,6 +104,10 @@ void har_qkv(torch::Tensor x, torch::Tensor params, int64_t w_off, int64_t b_off
   const int64_t C = params.size(0), Lp = qkv.size(2);
   rows64(x, C, B * L, "x");
   headmajor(qkv, C, B, Lp, "qkv");
+  TORCH_CHECK(Lp % 64 == 0 && Lp >= L && L >= 1, "qkv: Lp must be a multiple of 64 and >= L");
+  const int64_t P = prow(params, C);
+  inrow(w_off, 192 * 64, P, "in_proj weight");
+  inrow(b_off, 192, P, "in_proj bias");
   AflHarQkv a{bf(x, "x"), f32(params, "params"), params.size(1), (int)w_off, (int)b_off, bf(qkv, "qkv"),
               (int)C, (int)B, (int)L, (int)Lp, (float)qscale};
   ok(afl_har_qkv(a, cur()), "har_qkv");
@@ -113,8 +136,8 @@ void har_post(torch::Tensor o, torch::Tensor x, torch::Tensor xh1, torch::Tensor
   a.rs = f32(rs, "rs");
   a.y = bf(y, "y");
   a.params = f32(params, "params");
-  a.P = params.size(1);
-  a.w = layer_w(w);
+  a.P = prow(params, C);
+  a.w = layer_w(w, a.P);
   a.C = (int)C;
   a.R = R;
   a.d1 = drop(seeds, stepctl, layer + 1, p);
@@ -128,6 +151,9 @@ AflHarAttn attn_args(torch::Tensor qkv, torch::Tensor lse2, int64_t B, int64_t L
                      c10::optional<torch::Tensor> stepctl, int64_t layer, double p) {
   const int64_t Lp = qkv.size(2), C = qkv.size(0) / (4 * B);
   headmajor(qkv, C, B, Lp, "qkv");
+  TORCH_CHECK(L >= 1 && Lp % 64 == 0 && Lp >= L, "attention: Lp must be a multiple of 64 and >= L");
+  TORCH_CHECK(Lp <= AFL_HAR_ATTN_MAX_LP, "attention: Lp ", Lp, " is above the cap ", AFL_HAR_ATTN_MAX_LP,
+              " (the dK / dV kernel's 72 Lp bytes of LDS must fit 64 KiB)");
   TORCH_CHECK(lse2.numel() == C * B * 4 * Lp, "lse2 must be [C*B*4, Lp]");
   AflHarAttn a{};
   a.qkv = bf(qkv, "qkv");
@@ -180,6 +206,8 @@ void har_post_bwd(c10::optional<torch::Tensor> dy, c10::optional<torch::Tensor> 
                   c10::optional<torch::Tensor> seeds, c10::optional<torch::Tensor> stepctl, int64_t layer, double p,
                   int64_t G, c10::optional<torch::Tensor> kbits) {
   const int64_t C = params.size(0), R = B * L;
+  TORCH_CHECK(G >= 1, "har_post_bwd: G must be >= 1");
+  TORCH_CHECK(B >= 1 && L >= 1, "har_post_bwd: B and L must be >= 1");
   for (auto* t : {&o, &xh1, &xh2, &dout}) rows64(*t, C, R, "activation");
   rows64(dres, C, R, "dres");
   AflHarPostB a{};
@@ -202,12 +230,13 @@ void har_post_bwd(c10::optional<torch::Tensor> dy, c10::optional<torch::Tensor> 
   a.dout = bf(dout, "dout");
   a.delta = f32(delta, "delta");
   a.Lp = (int)(delta.numel() / (C * B * 4));
-  TORCH_CHECK(delta.numel() == C * B * 4 * (int64_t)a.Lp && a.Lp >= L, "delta must be [C*B*4, Lp]");
+  TORCH_CHECK(delta.numel() == C * B * 4 * (int64_t)a.Lp && a.Lp >= L && a.Lp % 64 == 0,
+              "delta must be [C*B*4, Lp] with Lp a multiple of 64 and >= L");
   TORCH_CHECK(ws.numel() >= C * G * (int64_t)AFL_HAR_POST_NG, "ws too small");
   a.ws = f32(ws, "ws");
   a.params = f32(params, "params");
-  a.P = params.size(1);
-  a.w = layer_w(w);
+  a.P = prow(params, C);
+  a.w = layer_w(w, a.P);
   a.C = (int)C;
   a.R = R;
   a.d1 = drop(seeds, stepctl, layer + 1, p);
@@ -220,7 +249,10 @@ void har_post_bwd(c10::optional<torch::Tensor> dy, c10::optional<torch::Tensor> 
 void har_qkv_bwd(torch::Tensor dqkv, torch::Tensor dres, torch::Tensor x, torch::Tensor dx, torch::Tensor ws,
                  torch::Tensor params, int64_t w_off, int64_t B, int64_t L, int64_t G) {
   const int64_t C = params.size(0), R = B * L, Lp = dqkv.size(2);
+  TORCH_CHECK(G >= 1, "har_qkv_bwd: G must be >= 1");
   headmajor(dqkv, C, B, Lp, "dqkv");
+  TORCH_CHECK(L >= 1 && Lp % 64 == 0 && Lp >= L, "dqkv: Lp must be a multiple of 64 and >= L");
+  inrow(w_off, 192 * 64, prow(params, C), "in_proj weight");
   rows64(dres, C, R, "dres");
   rows64(x, C, R, "x");
   rows64(dx, C, R, "dx");
@@ -233,7 +265,9 @@ void har_qkv_bwd(torch::Tensor dqkv, torch::Tensor dres, torch::Tensor x, torch:
 void har_reduce(torch::Tensor ws, int64_t G, int64_t n, torch::Tensor seg, torch::Tensor grads) {
   dense(seg, "seg", torch::kInt32);
   TORCH_CHECK(seg.dim() == 2 && seg.size(1) == 3, "seg must be [nseg, 3]");
+  TORCH_CHECK(grads.dim() == 2, "grads must be [C, P]");
   const int64_t C = grads.size(0);
+  TORCH_CHECK(G >= 1 && n >= 1 && seg.size(0) >= 1, "har_reduce: G, n and the segment count must be >= 1");
   TORCH_CHECK(ws.numel() >= C * G * n, "ws too small");
   ok(afl_har_reduce(f32(ws, "ws"), (int)C, (int)G, (int)n, seg.data_ptr<int>(), (int)seg.size(0), f32(grads, "grads"),
                     grads.size(1), cur()),
@@ -266,4 +300,5 @@ void afl_register_har(pybind11::module& m) {
   m.def("har_blocks", [](int64_t R) { return afl_har_blocks(R); });
   m.attr("har_post_ng") = py::int_(AFL_HAR_POST_NG);
   m.attr("har_qkv_ng") = py::int_(AFL_HAR_QKV_NG);
+  m.attr("har_attn_max_lp") = py::int_(AFL_HAR_ATTN_MAX_LP);
 }

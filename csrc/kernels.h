@@ -416,6 +416,9 @@ struct AflHarAttn {
 };
 // keep words per (client, sample, head): [query tile Lp/16][key chunk Lp/64][t 4][e 4], bit = lane of the forward
 #define AFL_HAR_MASK_WORDS(Lp) ((long)((Lp) / 16) * ((Lp) / 64) * 16)
+// largest Lp the attention launchers admit: their dynamic LDS (forward 66 Lp, dK / dV 72 Lp, dQ 64 Lp bytes) stays
+// within the 64 KiB a launch gets without raising the kernel's dynamic shared-memory limit
+#define AFL_HAR_ATTN_MAX_LP 896
 #define AFL_HAR_KBITS_PER_ROW 16  // u32 words of AflHarPost::kbits per row
 #define AFL_HAR_POST_NG (64 * 64 + 256 * 64 + 64 * 256 + 640)
 #define AFL_HAR_QKV_NG (192 * 64 + 192)

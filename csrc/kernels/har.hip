@@ -1184,7 +1184,7 @@ __global__ void __launch_bounds__(256) k_har_reduce(const float* __restrict__ ws
   int k = 0;
   while (k + 1 < nseg && e >= seg[3 * (k + 1)]) ++k;
   const int off = e - seg[3 * k];
-  if (off >= seg[3 * k + 2]) return;
+  if (off < 0 || off >= seg[3 * k + 2]) return;  // (before the first segment, or in a gap between two)
   const float* w = ws + (long)c * G * n + e;
   float s = 0.f;
   for (int i = 0; i < G; ++i) s += w[(long)i * n];
@@ -1223,9 +1223,11 @@ int afl_har_qkv(const AflHarQkv& a, hipStream_t s) {
 }
 
 int afl_har_attn_fwd(const AflHarAttn& a, hipStream_t s) {
-  if (a.Lp % 64 || a.Lp < a.L || a.Lp > 1024) return (int)hipErrorInvalidValue;
+  if (a.Lp % 64 || a.Lp < a.L || a.Lp > AFL_HAR_ATTN_MAX_LP) return (int)hipErrorInvalidValue;
+  if (a.L < 1 || a.C < 1 || a.B < 1) return (int)hipErrorInvalidValue;
   if (a.drop.thr16 && !a.mask) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)a.Lp * 32 * 2 + (size_t)a.Lp * 2;  // K, V images + the column-pair hash table
+  static_assert(AFL_HAR_ATTN_MAX_LP % 64 == 0 && AFL_HAR_ATTN_MAX_LP * 72 <= 64 * 1024, "attention LDS fits 64 KiB");
   if (a.drop.thr16)
     hipLaunchKernelGGL(k_har_attn_fwd<true>, dim3(a.C * a.B * NH), dim3(AT_NT), lds, s, a);
   else
@@ -1234,7 +1236,8 @@ int afl_har_attn_fwd(const AflHarAttn& a, hipStream_t s) {
 }
 
 int afl_har_attn_bwd(const AflHarAttn& a, hipStream_t s) {
-  if (a.Lp % 64 || a.Lp < a.L || a.Lp > 1024) return (int)hipErrorInvalidValue;
+  if (a.Lp % 64 || a.Lp < a.L || a.Lp > AFL_HAR_ATTN_MAX_LP) return (int)hipErrorInvalidValue;
+  if (a.L < 1 || a.C < 1 || a.B < 1) return (int)hipErrorInvalidValue;
   if (a.drop.thr16 && !a.mask) return (int)hipErrorInvalidValue;
   const size_t kv = (size_t)a.Lp * 32 * 2 + (size_t)a.Lp * 8, dq = (size_t)a.Lp * 32 * 2;
   const dim3 grid(a.C * a.B * NH);
@@ -1251,13 +1254,14 @@ int afl_har_attn_bwd(const AflHarAttn& a, hipStream_t s) {
 int afl_har_blocks(long R) { return har_blocks(R); }
 
 int afl_har_post_bwd(const AflHarPostB& a, int G, hipStream_t s) {
+  if (G < 1 || a.Lp % 64 || a.Lp < a.L || ((a.d1.thr16 || a.df.thr16 || a.d2.thr16) && !a.kbits))
+    return (int)hipErrorInvalidValue;
   static bool attr = false;
   if (!attr) {
     if (hipFuncSetAttribute((const void*)k_har_post_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, PB_SMEM) != hipSuccess)
       return -2;
     attr = true;
   }
-  if (G < 1 || ((a.d1.thr16 || a.df.thr16 || a.d2.thr16) && !a.kbits)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_har_post_bwd, dim3(G, a.C), dim3(NTR), PB_SMEM, s, a);
   return (int)hipGetLastError();
 }
@@ -1275,18 +1279,19 @@ int afl_har_qkv_bwd(const AflHarQkvB& a, int G, hipStream_t s) {
 }
 
 int afl_har_reduce(const float* ws, int C, int G, int n, const int* seg, int nseg, float* grads, long P, hipStream_t s) {
+  if (G < 1 || n < 1 || nseg < 1) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_har_reduce, dim3((n + 255) / 256, C), dim3(256), 0, s, ws, G, n, seg, nseg, grads, P);
   return (int)hipGetLastError();
 }
 
 int afl_har_post(const AflHarPost& a, hipStream_t s) {
+  if ((a.d1.thr16 || a.df.thr16 || a.d2.thr16) && !a.kbits) return (int)hipErrorInvalidValue;
   static bool attr = false;
   if (!attr) {
     if (hipFuncSetAttribute((const void*)k_har_post, hipFuncAttributeMaxDynamicSharedMemorySize, PF_SMEM) != hipSuccess)
       return -2;
     attr = true;
   }
-  if ((a.d1.thr16 || a.df.thr16 || a.d2.thr16) && !a.kbits) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_har_post, dim3(har_blocks(a.R, a.C), a.C), dim3(NTP), PF_SMEM, s, a);
   return (int)hipGetLastError();
 }
