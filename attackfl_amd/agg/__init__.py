@@ -19,8 +19,8 @@ Beyond the reference (docs/PARITY.md): multi_krum, bulyan, dnc (assumed Byzantin
 cclip (centred clipping about the global model the round started from: the one rule that takes ``centre``).
 Pre-aggregation in front of a rule (engine ``pre-agg``): ``nnm`` (nearest-neighbour mixing) and ``bucketing``.
 ``foolsgold`` (FoolsGold) is the one stateful rule: it takes and returns the clients' update history, so it is called by
-name (``fl/engine.py`` ``_foolsgold``) and is not an entry of AGGREGATORS, the table of stateless rules.
-FLTrust and the hypernetwork live in the engine (``fl/engine.py`` ``_fltrust``, ``fl/hyper_server.py``): they train.
+name (``fl/server_modes.py`` ``FoolsGoldMode``) and is not an entry of AGGREGATORS, the table of stateless rules.
+FLTrust and the hypernetwork are server modes of their own (``fl/server_modes.py``, ``fl/hyper_server.py``): they train.
 """
 from __future__ import annotations
 

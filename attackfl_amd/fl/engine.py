@@ -35,11 +35,10 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..agg import AGGREGATORS, AggResult, pre_aggregate
-from ..agg import foolsgold as agg_foolsgold
+from ..agg import AGGREGATORS
 from ..agg import host_info as agg_host_info
 from ..attacks import DistanceEngine, host_info, run_attack
-from ..config import FOOLSGOLD_KAPPA, RULE_KNOBS, AttackSpec, Config
+from ..config import RULE_KNOBS, AttackSpec, Config
 from ..data import DeviceTable, resolve_dataset
 from ..detect import HyperDetector
 from ..eval import Validation
@@ -50,11 +49,12 @@ from ..utils import trace
 from ..utils.ckpt import CheckpointWriter
 from ..utils.log import Logger, MetricsWriter, NullLogger, print_with_color
 from .hyper_server import HyperServer
+from .server_modes import MODES, ServerMode
 from .trainers import Pending, Plan, make_plan, make_trainer
 
 # every rule of AGGREGATORS runs on the device without a host read (gmm up to 64 rows; its success is a device
 # bool): with one of them the aggregate and the next round's launch are enqueued before the host waits for the
-# training, as for FedAvg, FLTrust and the native hypernetwork update (FLEngine._early_ok, _early_launch)
+# training, as for FedAvg, FLTrust and the native hypernetwork update (ServerMode.early_ok, FLEngine._early_launch)
 EARLY_AGGREGATORS = tuple(m for m in AGGREGATORS if m != "fedavg")
 
 META = 5  # valid, result, size, is_attacker, decision word; then the client's per-epoch losses (E columns)
@@ -199,9 +199,7 @@ class Launch:
 class EarlyLaunch:
     """An early launch (``FLEngine._early_launch``): what its server step reported and what undoing it needs."""
     g_old: Optional[torch.Tensor]            # the global model before the step
-    fl_old: Optional[torch.Tensor]           # FLTrust's server model before the step
-    fg_old: Optional[tuple]                  # foolsgold: (history buffer in use, round count) before the step
-    hyper_step: Optional[int]                # the hypernetwork's step count before the step
+    mode_mark: object                        # the server mode's ``mark()`` before the step, for its ``undo``
     snap: tuple                              # (per local client (rng state, training round, genuine), server rng state)
     prep: Optional[Prepared]                 # the next launch's host half, staged ahead
     info: dict = field(default_factory=dict)  # the server step's info
@@ -269,7 +267,8 @@ class FLEngine:
         # ---- data (train set shared by all clients, resident on this rank's device) ----
         self.local = [LocalClient(ci, random.Random(self.seed * 7919 + ci.index), self.seed * 104729 + ci.index)
                       for ci in self.table if ci.owner == self.rank]
-        need_train = len(self.local) > 0 or self.mode == "FLTrust"
+        mode_cls = MODES[self.mode]  # (the one place that maps the mode's name to its ServerMode)
+        need_train = len(self.local) > 0 or mode_cls.needs_train_table
         self.train_table = None
         if need_train:
             ds = train_dataset if train_dataset is not None else resolve_dataset(self.data_name, "train", cfg.data,
@@ -298,19 +297,11 @@ class FLEngine:
         self.selected: List[int] = []
         self._selection_done = False
         self.genuine_pool: Optional[torch.Tensor] = None
-        self.hyper: Optional[HyperServer] = None
-        self.fltrust_model: Optional[torch.Tensor] = None
-        # foolsgold (replicated, every rank its own identical copy): the clients' update histories [n_clients, P] in
-        # two ping-pong buffers (a step reads one and writes the other, so undoing it is switching back), which one is
-        # in use, and the successful rounds accumulated (a 0-d int64 tensor: the device counts in the early launch)
-        self._fg_bufs: Optional[List[torch.Tensor]] = None
-        self._fg_cur = 0
-        self.fg_rounds: Optional[torch.Tensor] = None
-        self._fg_ids = None
+        self.hyper: Optional[HyperServer] = None      # (both set by HyperMode)
         self.detector: Optional[HyperDetector] = None
         self.torch_gen = torch.Generator(device=self.device if self.device.type == "cuda" else "cpu")
         self.torch_gen.manual_seed(self.seed * 31337 + self.rank)
-        self._init_server()
+        self.server: ServerMode = mode_cls(self)  # the mode's work and its state (fl/server_modes.py)
         self.round_no = 1
         self.rounds_left = cfg.num_round
         self.history: List[dict] = []
@@ -336,14 +327,12 @@ class FLEngine:
         self._spec: Optional[Launch] = None  # the next round's launch, enqueued ahead (speculative / early)
         self._next_prep: Optional[Prepared] = None  # the next launch's host half, staged while this training runs
         self._start_ready = None  # event: the latest launch's START models are generated (the validation stream waits)
-        self._attack_info = self._trust = None  # the round in progress: the last attack's info, FLTrust's scores
-        self._fl_pending = None  # FLTrust's server-model training, checked at the round's end
+        self._attack_info = None  # the round in progress: the last attack's info
         self._sel_cache = None
         self._rows_idx: dict = {}  # _take_rows: index lists already on the device
         self._staging = Staging(self.device)
-        # created on first use: GPU streams, the meta read's pinned buffer, FLTrust's root set, hyper's checkpoint tail
-        self._val_stream = self._side = self._stage_stream = None
-        self._meta_pinned = self._fl_root = self._hyper_tail = None
+        # created on first use: GPU streams, the meta read's pinned buffer
+        self._val_stream = self._side = self._stage_stream = self._meta_pinned = None
         self._has_attackers = any(ci.attack is not None for ci in self.table)
         self._speculative = (bool(cfg.engine.get("speculative", True)) and self.device.type == "cuda"
                              and not cfg.hyper_detection.get("enable", False) and not cfg.load_parameters
@@ -361,66 +350,16 @@ class FLEngine:
             return os.path.join(self.ckpt_dir, f"{self.model_name}_hyper_{self.cfg.clients}.pth")
         return os.path.join(self.ckpt_dir, f"{self.model_name}.pth")
 
-    def _init_server(self):
-        cfg = self.cfg
-        if self.mode == "hyper":
-            net = build_model(self.model_name, seed=self.seed + 99)
-            target_sd = net.state_dict()
-            hyper_ckpt = None
-            if cfg.load_parameters:
-                if os.path.exists(self._pth(True)):
-                    hyper_ckpt = torch.load(self._pth(True), weights_only=True, map_location="cpu")
-                elif os.path.exists(self._pth(False)):
-                    net.load_state_dict(torch.load(self._pth(False), weights_only=True, map_location="cpu"))
-                    target_sd = net.state_dict()
-            self.hyper = HyperServer(target_sd, cfg.clients, cfg.hyper_lr, cfg.clip_grad_norm, self.device,
-                                     seed=self.seed)
-            if hyper_ckpt is not None:
-                if cfg.engine.get("compat-hyper-resume", False):
-                    print_with_color("[compat A-5] hyper checkpoint loaded then discarded", "yellow")
-                else:
-                    self.hyper.hnet.load_state_dict(hyper_ckpt)
-                    print_with_color(f"Load state dict from hyper model: {self._pth(True)}", "yellow")
-            hd = cfg.hyper_detection
-            if hd.get("enable", False):
-                # replicated like validation (the embeddings are bit-identical on every rank; PCA / DBSCAN are
-                # deterministic host code); only the leader writes all_embeddings.npy and prints
-                self.detector = HyperDetector(cfg.clients, int(hd.get("n_components", 3)), float(hd.get("eps", 0.007)),
-                                              int(hd.get("min_samples", 3)),
-                                              save_path=os.path.join(self.ckpt_dir, "all_embeddings.npy")
-                                              if self.leader else "", verbose=self.leader)
-        if self.mode == "FLTrust":
-            m = build_model(self.model_name, seed=self.seed + 77)
-            self.fltrust_model = self.layout.flatten(m.state_dict(), device=self.device)
-        if self.mode == "foolsgold":
-            self._fg_bufs = [torch.zeros(self.n_clients, self.P, dtype=torch.float32, device=self.device)
-                             for _ in range(2)]
-            self.fg_rounds = torch.zeros((), dtype=torch.int64, device=self.device)
-
     def save_checkpoint(self):
         """Reference ``server.py:551-553`` (same files and keys).  Every rank remembers the saved
         global model (what ``{model}.pth`` now holds) so ``load: True`` rounds need no file read;
-        the leader writes the file in the background (``utils/ckpt.py``)."""
-        if self.mode != "hyper" and self.global_params is not None:
+        the leader writes the mode's file in the background (``ServerMode.checkpoint``, ``utils/ckpt.py``)."""
+        if self.global_params is not None:  # (the hypernetwork's rounds have none)
             self._saved_params = self.global_params.detach().clone()
         if not self.leader:
             return
         os.makedirs(self.ckpt_dir, exist_ok=True)
-        if self.mode == "hyper":
-            hnet = self.hyper.hnet
-            # deferred: the arena's copy is issued after the next training launch (utils/ckpt.py)
-            if self._hyper_tail is None:
-                self._hyper_tail = hnet.target_tail()
-            self.ckpt_writer.submit("hyper", hnet.arena, lambda a: hnet.state_dict_of(a, clone=False),
-                                    self._pth(True), defer=True, tail=self._hyper_tail)
-        elif self.global_params is not None:
-            layout = self.layout
-            # deferred too: an immediate copy let the writer thread's torch.save (GIL-bound, ~0.5 ms) run
-            # in the gap between two rounds' training launches and stall the next round's preparation;
-            # kicked after the next launch it runs while the GPU trains.  global_params is replaced, never
-            # updated in place, so the submitted tensor stays valid until the copy.
-            self.ckpt_writer.submit("global", self.global_params, lambda f: layout.unflatten(f, clone=False),
-                                    self._pth(False), defer=True)
+        self.server.checkpoint()
 
     # ---- resumable run state (new: the reference persists only the model, SURVEY §5.4) ----
     def _state_paths(self):
@@ -438,12 +377,8 @@ class FLEngine:
             srv = {"round_no": self.round_no, "rounds_left": self.rounds_left, "rng_version": v,
                    "rng_state": list(st), "rng_gauss": gauss, "selected": list(self.selected),
                    "global": self.global_params.detach().cpu() if self.global_params is not None else None,
-                   "genuine_pool": self.genuine_pool.detach().cpu() if self.genuine_pool is not None else None}
-            if self._fg_bufs is not None:
-                srv.update(fg_history=self.fg_history.detach().cpu(), fg_rounds=int(self.fg_rounds))
-            if self.hyper is not None:
-                srv.update(hyper_arena=self.hyper.hnet.arena.detach().cpu(), hyper_m=self.hyper.m.cpu(),
-                           hyper_v=self.hyper.v.cpu(), hyper_step=self.hyper.step)
+                   "genuine_pool": self.genuine_pool.detach().cpu() if self.genuine_pool is not None else None,
+                   **self.server.state()}
             torch.save(srv, srv_path + ".tmp")
             os.replace(srv_path + ".tmp", srv_path)
         cli = {"params": self.local_params.detach().cpu(), "index": [lc.info.index for lc in self.local],
@@ -467,14 +402,7 @@ class FLEngine:
             self.global_params = srv["global"].to(self.device)
         if srv.get("genuine_pool") is not None:
             self.genuine_pool = srv["genuine_pool"].to(self.device)
-        if self.hyper is not None and "hyper_m" in srv:
-            self.hyper.load_arena(srv["hyper_arena"])
-            self.hyper.m.copy_(srv["hyper_m"])
-            self.hyper.v.copy_(srv["hyper_v"])
-            self.hyper.step = int(srv["hyper_step"])
-        if self._fg_bufs is not None and "fg_history" in srv:
-            self._fg_bufs[self._fg_cur].copy_(srv["fg_history"].to(self.device))
-            self.fg_rounds = torch.as_tensor(int(srv["fg_rounds"]), dtype=torch.int64).to(self.device)
+        self.server.load(srv)
         if os.path.exists(cli_path):
             cli = torch.load(cli_path, weights_only=True, map_location="cpu")
             self.local_params.copy_(cli["params"].to(self.device))
@@ -492,9 +420,8 @@ class FLEngine:
         self.selected = list(range(self.n_clients))
         self.logger.log_info(f"Active with {len(self.selected)} client: {self.selected}")
 
-    def _start_params(self, i: int) -> Optional[torch.Tensor]:
-        if self.mode == "hyper":
-            return self.hyper.generate(i)
+    def _start_params(self) -> Optional[torch.Tensor]:
+        """The model every client starts the round from, where the mode has one (``ServerMode.start``)."""
         if self.cfg.load_parameters:
             if self._saved_params is not None:  # == the file this run last wrote
                 return self._saved_params
@@ -686,11 +613,7 @@ class FLEngine:
         block = None if plain else torch.zeros(self.slots, self.W, dtype=torch.float32, device=dev)
         # START parameters of every started client (one batched generate / broadcast copy)
         if prep.clients:
-            if self.mode == "hyper":
-                start = self.hyper.generate_many([i for _, i, _, _ in prep.clients])
-            else:
-                p = self._start_params(prep.clients[0][1])
-                start = None if p is None else p[None, :].expand(len(js), -1)
+            start = self.server.start([i for _, i, _, _ in prep.clients])
             if start is not None:
                 if js == list(range(len(js))):
                     self.local_params[:len(js)].copy_(start)
@@ -819,7 +742,7 @@ class FLEngine:
 
     def _server_step(self, U: torch.Tensor, sizes: torch.Tensor, attackers: torch.Tensor,
                      ok_all: Optional[torch.Tensor], w: Optional[torch.Tensor] = None, gen_key=None):
-        """The server rule of ``self.mode`` on the update rows ``U`` — the only place that maps the mode to work.
+        """The server mode's step (``ServerMode.step``) on the update rows ``U``: the single entry of both paths.
         ``ok_all`` None: the host knows that every client succeeded (the serial path, ``_aggregate``).  A 0-d device
         bool, "every client succeeded" as the device knows it (``_early_launch``): nothing is read back, the new
         global model is ``where(ok_all [& the rule's success], new, old)`` and the hypernetwork update gets it as
@@ -827,56 +750,9 @@ class FLEngine:
         pass.  ``w``: FedAvg weights already on the device (each caller keeps its own source); ``gen_key``: the clients
         whose next START models the hypernetwork update generates.  Returns (info, the rule's own success: None =
         always, or a 0-d tensor — gmm).  ``engine.pre-agg`` (nnm, bucketing: ``agg.pre_aggregate``) goes in front of a
-        rule of AGGREGATORS on either path.  What a failed early round rolls back stays on ``self`` (``fltrust_model``,
-        ``_trust``, ``_fl_pending``, ``hyper.step``, foolsgold's history buffer and round count:
-        ``_early_launch_failed``)."""
-        mode, g_old = self.mode, self.global_params
-        if mode == "hyper":
-            self.ckpt_writer.fence()  # the previous round's checkpoint copy of the arena, updated in place below
-            # (a device ok_all: the update runs, or leaves the hypernetwork untouched, as the device decides)
-            kw = {} if ok_all is None else {"enable": ok_all.to(torch.int32).reshape(1), "gen_key": gen_key}
-            self.hyper.train(self.selected, {i: U[k] for k, i in enumerate(self.selected)}, **kw)
-            return {"_lazy": lambda: self.hyper.last_info}, None  # read after validation: no sync between them
-        if mode == "FLTrust":
-            new = self._fltrust(U)
-            self.global_params = new if ok_all is None else torch.where(ok_all, new, g_old)
-            return {}, None
-        if mode == "foolsgold":
-            new, info = self._foolsgold(U, sizes, ok_all)
-            self.global_params = new if ok_all is None else torch.where(ok_all, new, g_old)
-            return info, None
-        if mode == "fedavg" and w is not None:
-            # the weights were staged with the launch (sizes known then): no host -> device copy here
-            if ok_all is None:
-                self.global_params = ops.weighted_rows(U, w)
-            elif ok_all.dim():
-                self.global_params = ops.weighted_rows(U, w, ok_all, g_old)  # (the success check fused into the pass)
-            else:
-                self.global_params = torch.where(ok_all, ops.weighted_rows(U, w), g_old)
-            return {"n": int(U.shape[0])}, None
-        args, pre = self._rule_args(), None
-        if self.cfg.engine.get("pre-agg", "none") != "none":
-            # (device work without a host read, like the rules: the rule then sees the mixed rows and their sizes)
-            U, sizes, pre = pre_aggregate(self.cfg.engine["pre-agg"], U, sizes, byz_f=args["byz_f"], seed=args["seed"],
-                                          bucket_size=self.cfg.engine.get("bucket-size", 2))
-        res: AggResult = AGGREGATORS[mode](U, sizes, attackers=attackers, **args)
-        info = {k: v for k, v in res.info.items() if k != "scores"}
-        if pre is not None:
-            info["pre_agg"] = pre
-        if ok_all is None:
-            if not bool(res.ok):  # (gmm on the device: a 0-d tensor, the serial path's one synchronising read)
-                info["agg_failed"] = True
-            elif res.params is not None:
-                g = res.params.to(torch.float32)
-                if g.untyped_storage().data_ptr() == U.untyped_storage().data_ptr():
-                    g = g.clone()  # a selected row (e.g. Krum) of U, which may be the live client models
-                self.global_params = g
-            return info, None
-        rule_ok = None if res.ok is True else torch.as_tensor(res.ok, device=U.device)
-        if res.params is not None:  # (a new tensor: never a row of U)
-            self.global_params = torch.where(ok_all if rule_ok is None else ok_all & rule_ok,
-                                             res.params.to(torch.float32), g_old)
-        return info, rule_ok
+        rule of AGGREGATORS on either path.  What a failed early round rolls back stays on the mode (``mark``,
+        ``undo``), the global model on ``self`` (``_early_launch_failed``)."""
+        return self.server.step(U, sizes, attackers, ok_all, w=w, gen_key=gen_key)
 
     def _aggregate(self, U: torch.Tensor, sizes: torch.Tensor, attackers: torch.Tensor, round_ok: bool,
                    w: Optional[torch.Tensor]) -> dict:
@@ -887,102 +763,6 @@ class FLEngine:
         if w is not None and not (U.is_cuda and U.shape[0] == w.shape[0]):
             w = None
         return self._server_step(U, sizes, attackers, None, w=w)[0]
-
-    @property
-    def fg_history(self) -> Optional[torch.Tensor]:
-        """foolsgold: the clients' update histories [n_clients, P], row = client id (None in every other mode)."""
-        return None if self._fg_bufs is None else self._fg_bufs[self._fg_cur]
-
-    def _foolsgold(self, U: torch.Tensor, sizes: torch.Tensor, ok_all: Optional[torch.Tensor]):
-        """FoolsGold (``agg.foolsgold``) on the selected clients' rows about the model the round started from, with the
-        engine's history: read from the buffer in use, written to the other one, which then becomes the one in use.
-        ``ok_all`` goes in as ``enable``, so a round that failed on the device leaves the history's bits (and the count
-        of rounds) as they were.  A selection that is a strict subset of the clients is gathered from and scattered to
-        its rows of the history by client id, the other rows copied.  Before there is a global model (round 1) the
-        result is FedAvg and nothing is accumulated.  -> (the new global model, info)."""
-        H, nxt = self._fg_bufs[self._fg_cur], self._fg_bufs[1 - self._fg_cur]
-        kappa = self.cfg.engine.get(FOOLSGOLD_KAPPA.key, FOOLSGOLD_KAPPA.default)
-        enable = None if ok_all is None else ok_all.all().to(torch.int32).reshape(1)
-        full = list(self.selected) == list(range(self.n_clients))
-        ids = None
-        if not full:
-            key = tuple(self.selected)
-            if self._fg_ids is None or self._fg_ids[0] != key:
-                ix = torch.tensor(self.selected, dtype=torch.long)
-                if self.device.type == "cuda":  # (pinned and non-blocking: no wait for the stream)
-                    from ..ops.layers import upload
-                    ix = upload(ix, self.device)
-                self._fg_ids = (key, ix)
-            ids = self._fg_ids[1]
-        res = agg_foolsgold(U, sizes, centre=self.global_params, history=H if full else H.index_select(0, ids),
-                            kappa=kappa, enable=enable, rounds=self.fg_rounds, out=nxt if full else None)
-        info = {k: v for k, v in res.info.items() if k != "history"}
-        if self.global_params is not None:  # (no centre: the history is untouched)
-            if not full:
-                nxt.copy_(H)
-                nxt.index_copy_(0, ids, res.info["history"])
-            self._fg_cur = 1 - self._fg_cur
-            self.fg_rounds = res.info["rounds"]
-        return res.params, info
-
-    def _fltrust_setup(self):
-        """Root set (first 200 test rows, ``server.py:290-293``), its device table and the server model's
-        trainer: built once and reused every round."""
-        if self._fl_root is None:
-            from ..data import ICUData
-
-            root = resolve_dataset(self.data_name, "test", self.cfg.data, verbose=False)
-            if isinstance(root, ICUData):
-                root = ICUData(vitals=root.vitals[:200], labs=root.labs[:200], labels=root.labels[:200])
-            table = DeviceTable(root, self.device)
-            trainer = make_trainer(self.cfg.engine.get("trainer", "auto"), self.model_name, self.data_name, table,
-                                   self.device)
-            nd = min(200, table.n)
-            # DataLoader(batch_size=100, shuffle=False): the same in-order visit every epoch
-            order = torch.arange(nd, dtype=torch.int32, device=self.device)[None, None, :].expand(
-                1, self.cfg.epoch, nd).contiguous()
-            plan = Plan(order, torch.tensor([nd], dtype=torch.int32), self.cfg.epoch,
-                        nd_dev=torch.tensor([nd], dtype=torch.int32, device=self.device))
-            self._fl_root = (table, trainer, plan)
-        return self._fl_root
-
-    def _fltrust(self, U: torch.Tensor) -> torch.Tensor:
-        """FLTrust with a server model trained on the first 200 test rows (``server.py:682-743``).
-        Everything stays on the device: the server model's training is enqueued (its result is ignored,
-        like the reference's ``train_on_device`` return value), and the trust scores, norms and the
-        trust-weighted sum are device tensors; ``trust`` reaches the JSONL lazily after validation."""
-        compat = bool(self.cfg.engine.get("compat-fltrust", False))
-        g0 = self.global_params if self.global_params is not None else self.fltrust_model.clone()
-        _, trainer, plan = self._fltrust_setup()
-        params = g0.clone()[None]
-        # kept and read at the round's host synchronisation (_finish_round): a NaN result is ignored like the
-        # reference's train_on_device return value, a cross-workgroup timeout still raises
-        seed = self.seed + self.round_no
-        ds = getattr(trainer, "device_seed", None)
-        seeds_dev = None
-        if ds is not None and self.device.type == "cuda":
-            # a pinned, non-blocking upload: the trainer's own upload of a host list is a pageable copy, which
-            # waits for the clients' training (the early launch enqueues this before that ends)
-            from ..ops.layers import upload
-            seeds_dev = upload(torch.tensor([ds(seed)], dtype=torch.int32), self.device)
-        self._fl_pending = trainer.launch(params, plan, self.cfg.lr, 100, [seed], seeds_dev=seeds_dev)
-        server_new = params[0]
-        g0_delta = server_new - g0
-        if compat and self.global_params is None:
-            g0_delta = torch.zeros_like(g0)  # round-1 alias: state_dict() views were trained in place
-        deltas = U - g0[None, :]
-        if compat:
-            deltas = deltas - g0[None, :]   # A-10: the stored delta is reduced by g_0 a second time
-        norm_g0 = torch.linalg.vector_norm(g0_delta.double())
-        norms = ops.row_norms(deltas).double()
-        cos = ops.cosine_to(deltas, g0_delta, eps=1e-8).double()
-        trust = torch.clamp(cos, min=0.0)
-        scale = (norm_g0 / (norms + 1e-6)) * trust
-        w = scale / (trust.sum() + 1e-6)
-        agg = ops.weighted_rows(deltas, w)
-        self.fltrust_model = server_new
-        self._trust = trust
-        return g0 + agg
 
     # ------------------------------------------------------------------------------------------
     # one round
@@ -999,7 +779,7 @@ class FLEngine:
         if self.verbose:
             print_with_color(f"Start training round {self.round_no}", "yellow")
         self._attack_info = None
-        self._trust = None
+        self.server.begin_round()
         with trace.range("fl/local"):
             launch, self._spec = self._spec, None
             if launch is None:
@@ -1035,8 +815,7 @@ class FLEngine:
             # stored updates (arrival in client order; the reference stops storing after a failure)
             if not round_ok:
                 stored = int(np.nonzero(~results)[0][0])
-            snapshot = self.hyper.snapshot() if (self.mode == "hyper" and self.cfg.hyper_detection.get("enable")) \
-                else None
+            snapshot = self.hyper.snapshot() if self.detector is not None else None  # (detection may roll back)
             if esl is not None:  # (several ranks: the aggregate and the next launch are in already)
                 round_ok, info = self._early_outcome(esl, results)
             else:
@@ -1050,8 +829,8 @@ class FLEngine:
         # ---- genuine pool for the next START (non-attacker rows stored this round; only attackers read it) ----
         if self._has_attackers and U is not None and esl is None:
             keep = self._store_genuine(U, stored)
-            if (keep and keep[0] == 0 and round_ok and self.mode == "fedavg" and self.global_params is not None
-                    and self.cfg.engine.get("compat-fedavg-alias", False)):
+            if (keep and keep[0] == 0 and round_ok and self.server.aliases_first_stored
+                    and self.global_params is not None):
                 # A-13: the reference averages INTO the first stored update's dict, which is also the first
                 # genuine model in the pool (server.py:263-268,763): attackers may receive the aggregate
                 self.genuine_pool[0] = self.global_params
@@ -1064,8 +843,8 @@ class FLEngine:
         if esl is not None and self._spec is not None:
             agg_done = esl.agg_done
         elif self._speculative and round_ok and self.rounds_left > 1 and not last:
-            if self.mode != "hyper":  # (test() falls back to the ordinary path if the model changes after this)
-                self._prefetch_validation(self.global_params)
+            # (no global model, as in hyper mode: nothing; test() falls back to the ordinary path if it changes later)
+            self._prefetch_validation(self.global_params)
             agg_done = torch.cuda.Event()
             agg_done.record(torch.cuda.current_stream(self.device))
             self._spec = self._launch_local(self._genuine_for_attackers())
@@ -1172,16 +951,10 @@ class FLEngine:
             self.validation.prefetch(g)
 
     def _early_ok(self, last: bool) -> bool:
-        """Which modes launch early (``_early_launch``): FedAvg, the hypernetwork's native update, FLTrust, foolsgold
-        (the device decides whether its history advances) and every rule of AGGREGATORS — all device work without a host read (gmm up to 64 rows)."""
-        if self.mode == "hyper":
-            mode_ok = self.device.type == "cuda" and self.hyper._native_ok()
-        else:
-            mode_ok = ((self.mode in ("fedavg", "FLTrust", "foolsgold") or self.mode in EARLY_AGGREGATORS)
-                       and not (self.mode == "gmm" and len(self.selected) > 64) and not self.fast_fedavg
-                       and self.global_params is not None
-                       and not self.cfg.engine.get("compat-fedavg-alias", False))
-        return self._speculative and mode_ok and self.rounds_left > 1 and not last
+        """Whether this round launches early (``_early_launch``).  The mode's half is ``ServerMode.early_ok``: FedAvg,
+        the hypernetwork's native update, FLTrust, foolsgold (the device decides whether its history advances) and
+        every rule of AGGREGATORS — all device work without a host read (gmm up to 64 rows)."""
+        return self._speculative and self.rounds_left > 1 and not last and self.server.early_ok()
 
     def _store_genuine(self, U: torch.Tensor, stored: int) -> List[int]:
         """The genuine pool of the next START: the non-attacker rows among the first ``stored`` of ``U`` (a new
@@ -1210,7 +983,7 @@ class FLEngine:
             n = len(self.selected)
             U = self.local_params[:n]
             ok_all = launch.pending.ok_device()[:n]
-            if not (self.mode == "fedavg" and ok_all.dtype == torch.int32):  # (FedAvg: reduced inside the aggregate)
+            if not (self.server.takes_ok_flags and ok_all.dtype == torch.int32):  # (FedAvg: reduced in the aggregate)
                 ok_all = (ok_all > 0).all()
             w, sizes = prep.fedavg_w, prep.sizes_h
             attackers = torch.from_numpy(prep.meta[self._local_rows(), 3] > 0.5)
@@ -1222,9 +995,7 @@ class FLEngine:
             attackers = sel[:, P + 3] > 0.5
         # (the snapshot already includes the staged host half's draws; its clients' START models come out of the
         # hypernetwork update's last launches)
-        esl = EarlyLaunch(g_old=self.global_params, fl_old=self.fltrust_model,
-                          fg_old=(self._fg_cur, self.fg_rounds) if self.mode == "foolsgold" else None,
-                          hyper_step=self.hyper.step if self.mode == "hyper" else None,
+        esl = EarlyLaunch(g_old=self.global_params, mode_mark=self.server.mark(),
                           snap=([(lc.rng.getstate(), lc.training_round, lc.genuine) for lc in self.local],
                                 self.server_rng.getstate()),
                           prep=self._next_prep)
@@ -1241,8 +1012,7 @@ class FLEngine:
         if self._has_attackers:  # the pool of a fully stored round
             esl.keep = self._store_genuine(U, len(self.selected))
             esl.pool = self.genuine_pool
-        if self.mode != "hyper":
-            self._prefetch_validation(self.global_params)
+        self._prefetch_validation(self.global_params)  # (no global model, as in hyper mode: nothing)
         esl.agg_done = torch.cuda.Event()
         esl.agg_done.record(torch.cuda.current_stream(self.device))
         self._spec = self._launch_local(self._genuine_for_attackers())
@@ -1264,15 +1034,7 @@ class FLEngine:
 
     def _early_launch_failed(self, esl: "EarlyLaunch", results: np.ndarray) -> None:
         self.global_params = esl.g_old  # (the device selected the same values: the launch's START)
-        if self.mode == "FLTrust":  # no server-model step and no trust scores for a failed round
-            self.fltrust_model = esl.fl_old
-            self._trust = None
-            self._fl_pending = None
-        if esl.fg_old is not None:  # the device kept the old history's bits: back to the buffer that holds them
-            self._fg_cur, self.fg_rounds = esl.fg_old
-        if esl.hyper_step is not None:  # the device skipped the hypernetwork update: its step count too
-            self.hyper.step = esl.hyper_step
-            self.hyper._info_dev = None
+        self.server.undo(esl.mode_mark)
         if esl.keep is None:
             return  # no attackers: the launch in flight is this round's retry
         # attackers sample the stored prefix's genuine rows: discard the launch, restore what it consumed
@@ -1319,17 +1081,8 @@ class FLEngine:
                     self.selected.remove(r)
             self.hyper.restore(snapshot)
         if self.validation is not None and round_ok:
-            if self.mode == "hyper":
-                round_ok, metric = self.validation.test_hyper(self.hyper, n_val)
-            else:
-                if self.global_params is None:
-                    round_ok = False
-                else:
-                    round_ok, metric = self.validation.test(self.global_params)
+            round_ok, metric = self.server.validate(n_val)
         trace.pop()
-        fl_pending, self._fl_pending = self._fl_pending, None
-        if fl_pending is not None:
-            fl_pending.result()  # (FLTrust's root training: finished by now; raises on a hand-off timeout)
         t4 = time.perf_counter()
         if round_ok:
             with trace.range("fl/checkpoint"):
@@ -1349,12 +1102,8 @@ class FLEngine:
         if self._attack_info:
             # every tried γ and its accept decision, not just the last one (the reference prints each γ)
             rec["attack"] = {k: v for k, v in host_info(self._attack_info).items() if isinstance(v, (int, float, list))}
-        lazy = info.pop("_lazy", None)
-        if lazy is not None:
-            info.update(lazy())
-        info = agg_host_info(info)  # (device-resident aggregator outputs: read now, after validation)
-        if self._trust is not None:
-            info["trust"] = [round(float(x), 6) for x in self._trust.tolist()]
+        # (device-resident outputs of the mode and the aggregator: read now, after validation)
+        info = agg_host_info(self.server.end_round(info))
         rec.update({k: v for k, v in info.items() if isinstance(v, (int, float, list, str)) or k == "pre_agg"})
         losses = self._client_losses(meta)
         if losses is not None:

@@ -59,6 +59,10 @@ class HyperServer:
             self._last_info = {"grad_norm": float(last[0]), "clip_scale": float(last[1])}
         return self._last_info
 
+    def drop_info(self) -> None:
+        """Forget the pending device info of an update that the device skipped (``enable`` 0)."""
+        self._info_dev = None
+
     # ------------------------------------------------------------------------------------------
     def generate(self, i: int) -> torch.Tensor:
         return self.hnet.generate(i)

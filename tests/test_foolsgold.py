@@ -306,13 +306,13 @@ def _cfg(path, rounds, **engine):
 
 def _capture(eng):
     """Every server step's rows and START model, taken before the step."""
-    seen, orig = [], eng._foolsgold
+    seen, orig = [], eng.server.foolsgold
 
     def cap(U, sizes, ok_all):
         seen.append((U.detach().clone(), None if eng.global_params is None else eng.global_params.detach().clone()))
         return orig(U, sizes, ok_all)
 
-    eng._foolsgold = cap
+    eng.server.foolsgold = cap
     return seen
 
 
@@ -323,10 +323,10 @@ def test_cpu_engine_history_is_the_sum_over_successful_rounds(tmp_path):
     seen = _capture(eng)
     oks, hists = [], []
     while eng.rounds_left > 0:
-        before = eng.fg_history.clone()
+        before = eng.server.history.clone()
         rec = eng.run_round()
         oks.append(rec["ok"])
-        hists.append((before, eng.fg_history.clone()))
+        hists.append((before, eng.server.history.clone()))
     eng.ckpt_writer.flush()
     assert oks == [True, False, True, True]
     # round 1 starts without a global model: FedAvg, nothing accumulated; the failed round never reached the rule
@@ -335,7 +335,7 @@ def test_cpu_engine_history_is_the_sum_over_successful_rounds(tmp_path):
     H = torch.zeros(4, eng.P)
     for U, g in seen[1:]:
         H = H + (U - g[None])
-    assert bool(H.any()) and torch.equal(eng.fg_history, H) and int(eng.fg_rounds) == 2
+    assert bool(H.any()) and torch.equal(eng.server.history, H) and int(eng.server.rounds) == 2
     eng.close()
     recs = [json.loads(line) for line in open(tmp_path / "m.jsonl")]
     ok_recs = [r for r in recs if r["ok"]]
@@ -351,7 +351,7 @@ def test_cpu_engine_stop_and_resume_is_exact(tmp_path):
     full = tmp_path / "full"
     eng = FLEngine(from_dict(_cfg(full, 4)), device="cpu", verbose=False)
     eng.run()
-    H_ref, n_ref = eng.fg_history.clone(), int(eng.fg_rounds)
+    H_ref, n_ref = eng.server.history.clone(), int(eng.server.rounds)
     eng.close()
     ref = torch.load(os.path.join(full, "TransformerModel.pth"), weights_only=True)
 
@@ -360,10 +360,10 @@ def test_cpu_engine_stop_and_resume_is_exact(tmp_path):
     eng.run(max_rounds=2)
     eng.close()
     eng2 = FLEngine(from_dict(_cfg(part, 4, **{"save-state": True, "resume": True})), device="cpu", verbose=False)
-    assert eng2.round_no == 3 and eng2.rounds_left == 2 and int(eng2.fg_rounds) == 1 and bool(eng2.fg_history.any())
+    assert eng2.round_no == 3 and eng2.rounds_left == 2 and int(eng2.server.rounds) == 1 and bool(eng2.server.history.any())
     hist = eng2.run()
     assert [r["round"] for r in hist] == [3, 4]
-    assert n_ref == 3 == int(eng2.fg_rounds) and torch.equal(eng2.fg_history, H_ref)
+    assert n_ref == 3 == int(eng2.server.rounds) and torch.equal(eng2.server.history, H_ref)
     eng2.close()
     got = torch.load(os.path.join(part, "TransformerModel.pth"), weights_only=True)
     assert list(ref) == list(got) and all(torch.equal(ref[k], got[k]) for k in ref)
@@ -379,21 +379,21 @@ def test_engine_subset_selection_is_keyed_by_client_id(tmp_path):
     sizes = torch.tensor([200.0, 180.0, 250.0])
     eng.selected = [0, 2, 3]
     U1 = g[None] + 0.01 * torch.randn(3, P, generator=gen)
-    new, info = eng._foolsgold(U1, sizes, None)
+    new, info = eng.server.foolsgold(U1, sizes, None)
     want = agg.foolsgold(U1, sizes, g, None, 1.0)
     assert torch.equal(new, want.params) and torch.equal(info["alpha"], want.info["alpha"]) and "history" not in info
-    assert torch.equal(eng.fg_history[[0, 2, 3]], U1 - g[None]) and not bool(eng.fg_history[1].any())
+    assert torch.equal(eng.server.history[[0, 2, 3]], U1 - g[None]) and not bool(eng.server.history[1].any())
     eng.selected = [1, 3]
     U2 = g[None] + 0.01 * torch.randn(2, P, generator=gen)
-    new, info = eng._foolsgold(U2, sizes[:2], torch.ones((), dtype=torch.bool))
+    new, info = eng.server.foolsgold(U2, sizes[:2], torch.ones((), dtype=torch.bool))
     H = torch.zeros(4, P)
     H[[0, 2, 3]] = U1 - g[None]
     want = agg.foolsgold(U2, sizes[:2], g, H[[1, 3]], 1.0)
     H[[1, 3]] = H[[1, 3]] + (U2 - g[None])
-    assert torch.equal(eng.fg_history, H) and torch.equal(new, want.params) and int(eng.fg_rounds) == 2
-    before = eng.fg_history.clone()
-    eng._foolsgold(U2, sizes[:2], torch.zeros((), dtype=torch.bool))  # a round the device saw fail
-    assert torch.equal(eng.fg_history, before) and int(eng.fg_rounds) == 2
+    assert torch.equal(eng.server.history, H) and torch.equal(new, want.params) and int(eng.server.rounds) == 2
+    before = eng.server.history.clone()
+    eng.server.foolsgold(U2, sizes[:2], torch.zeros((), dtype=torch.bool))  # a round the device saw fail
+    assert torch.equal(eng.server.history, before) and int(eng.server.rounds) == 2
     eng.close()
 
 
@@ -418,7 +418,7 @@ def test_two_ranks_carry_the_history(tmp_path):
     srv = torch.load(tmp_path / "mp" / "TransformerModel.state.pt", weights_only=True)
     eng = FLEngine(from_dict(_cfg(tmp_path / "sp", 3)), device="cpu", verbose=False)
     eng.run()
-    H, count = eng.fg_history.clone(), int(eng.fg_rounds)
+    H, count = eng.server.history.clone(), int(eng.server.rounds)
     eng.close()
     assert srv["fg_rounds"] == count == 2 and srv["fg_history"].shape == H.shape and bool(H.any())
     assert torch.allclose(srv["fg_history"], H, atol=1e-4)

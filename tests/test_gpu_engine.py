@@ -252,16 +252,16 @@ def test_robust_modes_end_to_end(gpu, tmp_path, monkeypatch, mode, attack):
         monkeypatch.setitem(AGGREGATORS, mode, capture)
     fl_seen = []
     if mode == "FLTrust":  # the rows, g_0 and the server model around every device FLTrust aggregate
-        orig_fl = eng._fltrust
+        orig_fl = eng.server.fltrust
 
         def cap_fl(U):
-            g0 = (eng.global_params if eng.global_params is not None else eng.fltrust_model).detach().cpu().clone()
+            g0 = (eng.global_params if eng.global_params is not None else eng.server.model).detach().cpu().clone()
             out = orig_fl(U)
-            fl_seen.append((U.detach().cpu().clone(), g0, eng.fltrust_model.detach().cpu().clone(),
+            fl_seen.append((U.detach().cpu().clone(), g0, eng.server.model.detach().cpu().clone(),
                             out.detach().cpu().clone()))
             return out
 
-        eng._fltrust = cap_fl
+        eng.server.fltrust = cap_fl
     hist = eng.run()
     eng.close()
     assert [r["ok"] for r in hist] == [True, True, True]

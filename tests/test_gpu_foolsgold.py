@@ -224,7 +224,7 @@ def test_early_launch_matches_serial_schedule(gpu, tmp_path, fault):
         seen = R._capture(eng)
         hist = eng.run()
         assert not spec or any(r.get("path") == "early-launch" for r in hist)
-        H, count, g = eng.fg_history.detach().cpu().clone(), int(eng.fg_rounds), eng.global_params.detach().cpu().clone()
+        H, count, g = eng.server.history.detach().cpu().clone(), int(eng.server.rounds), eng.global_params.detach().cpu().clone()
         eng.close()
         ck = torch.load(os.path.join(tmp_path, sub, "TransformerModel.pth"), weights_only=True)
         return [(r["ok"], None if r["metric"] != r["metric"] else r["metric"], r.get("alpha")) for r in hist], \
