@@ -16,7 +16,8 @@ Each rule returns ``AggResult(params [P] | None, ok, info)``.  Rows are in clien
 * fltracer      ``src/Utils.py:359-369`` (dormant in the reference)  PCA(1) + MAD z-score
 * byzantine     ``src/Utils.py:218-248`` (dead code in the reference) cosine ≥ 0.9 to model 0
 Beyond the reference (docs/PARITY.md): multi_krum, bulyan, dnc (assumed Byzantine count ``byz-f``), geomed (RFA) and
-cclip (centred clipping about the global model the round started from: the one rule that takes ``centre``).
+cclip (centred clipping about the global model the round started from) and signguard (SignGuard: a norm filter about the
+median norm and a mean-shift clustering of the rows' sign statistics); the last two are the rules that take ``centre``.
 Pre-aggregation in front of a rule (engine ``pre-agg``): ``nnm`` (nearest-neighbour mixing) and ``bucketing``.
 ``foolsgold`` (FoolsGold) is the one stateful rule: it takes and returns the clients' update history, so it is called by
 name (``fl/server_modes.py`` ``FoolsGoldMode``) and is not an entry of AGGREGATORS, the table of stateless rules.
@@ -32,6 +33,7 @@ import torch
 
 from .. import ops
 from ..config import BUCKET_SIZE, FOOLSGOLD_KAPPA, KNOB, PRE_AGG_KINDS  # (a knob's default and check: stated once, in config)
+from ..config import SIGNGUARD_FRAC, SIGNGUARD_HI, SIGNGUARD_LO
 from ..ops.composite import gmm_filter_ref  # noqa: F401  (the kernel's host mirror: tools and tests import it here)
 
 
@@ -236,6 +238,40 @@ def dnc(U: torch.Tensor, sizes=None, byz_f=KNOB["byz_f"].default, dnc_iters: int
     return AggResult(out, True, {"selected": keep, "f": f, "drop": drop, "scores": scores})
 
 
+def signguard(U: torch.Tensor, sizes=None, centre: Optional[torch.Tensor] = None, seed: int = 0,
+              signguard_frac=SIGNGUARD_FRAC.default, signguard_lo=SIGNGUARD_LO.default,
+              signguard_hi=SIGNGUARD_HI.default, **_) -> AggResult:
+    """SignGuard (Xu, Huang, Qu & Song, ICDCS 2022; beyond the reference, rule text in docs/PARITY.md) about ``centre``
+    g, the global model the round started from: a row passes when its norm ||x_i - g|| lies in [lo M, hi M], M the
+    lower median norm, and when it falls into the largest mean-shift cluster of the rows' sign statistics (the shares of
+    positive, zero and negative differences on a window of ceil(frac P) contiguous columns placed by ``seed``); the
+    result is g + sum_i c_i (x_i - g) over the kept rows with c_i = alpha_i min(1, M / norm_i) / sum_kept alpha,
+    alpha = sizes / sum sizes, and g itself when no row is kept.  Device, n <= 64: three launches (``k_sign_stats``,
+    ``k_signguard_select``, ``k_anchored_rows``), no host read.  Without a centre the result is FedAvg, every row kept.
+    info = {kept, norm_ok, cluster, scores (the features [n, 3]), weights, median_norm, bandwidth, window [s, b]}.
+    Always a new tensor."""
+    n, P = U.shape
+    frac, lo, hi = (k.check(v, coerce=True) for k, v in ((SIGNGUARD_FRAC, signguard_frac), (SIGNGUARD_LO, signguard_lo),
+                                                         (SIGNGUARD_HI, signguard_hi)))
+    if lo > hi:
+        raise ValueError(f"signguard: signguard-lo must be <= signguard-hi (got {lo}, {hi})")
+    a = _device_weights(sizes, U.device, n)
+    alpha = a / a.sum()
+    if centre is None:
+        s, b = ops.signguard_window(P, frac, seed)
+        one = torch.ones(n, dtype=torch.bool, device=U.device)
+        zero = torch.zeros((), dtype=torch.float64, device=U.device)
+        return AggResult(ops.fedavg(U, a if sizes is None else sizes), True,
+                         {"kept": one, "norm_ok": one.clone(), "cluster": torch.zeros(n, dtype=torch.int64, device=U.device),
+                          "scores": torch.zeros(n, 3, dtype=torch.float64, device=U.device), "weights": alpha,
+                          "median_norm": zero, "bandwidth": zero.clone(), "window": [s, b]})
+    g = centre.to(device=U.device, dtype=torch.float32)
+    keep, ok, label, F, c, M, h, (s, b) = ops.signguard_filter(U, g, frac, seed, alpha, lo, hi)
+    return AggResult(ops.anchored_rows(U, c, g), True,
+                     {"kept": keep, "norm_ok": ok, "cluster": label, "scores": F, "weights": c, "median_norm": M,
+                      "bandwidth": h, "window": [s, b]})
+
+
 def shieldfl(U: torch.Tensor, sizes=None, **_) -> AggResult:
     norms = ops.row_norms(U).to(U.device)
     Un = U / (norms.to(U.dtype)[:, None] + 1e-8)
@@ -382,6 +418,7 @@ AGGREGATORS = {
     "geomed": geomed,
     "dnc": dnc,
     "cclip": cclip,
+    "signguard": signguard,
     "shieldfl": shieldfl,
     "gmm": gmm,
     "scionfl": scionfl,

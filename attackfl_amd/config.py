@@ -24,10 +24,11 @@ Extensions (all optional, defaults keep reference behaviour):
   synthetic: auto | true | false   (auto = use the reference pickles when present)
   train-size / test-size / seed / har-train-size / har-test-size
 ``server:``
-  mode: the reference's modes plus multi_krum | bulyan | geomed | dnc | cclip | foolsgold (Multi-Krum, Bulyan, the
-        geometric median / RFA, Divide-and-Conquer and centred clipping: defences that assume f >= 1 Byzantine clients;
-        ``krum`` keeps the reference's f = 0, A-11; FoolsGold: the one rule with memory across rounds, a per-client
-        history of updates whose cosines weigh colluders down; definitions in docs/PARITY.md)
+  mode: the reference's modes plus multi_krum | bulyan | geomed | dnc | cclip | foolsgold | signguard (Multi-Krum,
+        Bulyan, the geometric median / RFA, Divide-and-Conquer and centred clipping: defences that assume f >= 1
+        Byzantine clients; ``krum`` keeps the reference's f = 0, A-11; FoolsGold: the one rule with memory across rounds,
+        a per-client history of updates whose cosines weigh colluders down; SignGuard: a norm filter about the median
+        norm and a clustering of the updates' sign statistics; definitions in docs/PARITY.md)
 ``engine:``
   trainer: auto | fused | graph | eager | oracle  (fused = HIP persistent TransformerModel / RNNModel
                                     kernels; graph = HIP-graph-replayed layer programs for CNN/RNN/HAR models;
@@ -65,6 +66,10 @@ Extensions (all optional, defaults keep reference behaviour):
   cclip-tau: auto | float > 0       (cclip: the clipping radius; auto, the default = the lower median of the rows'
                                     distances to the round's starting model, found on the device every round)
   foolsgold-kappa: float > 0        (foolsgold: the logit's confidence scale, default 1.0)
+  signguard-frac: float > 0         (signguard: the fraction of the columns whose signs are counted, one contiguous
+                                    window placed by the round's seed, default 0.1; >= 1 = every column)
+  signguard-lo: float > 0           (signguard: a row passes the norm filter from lo times the median norm, default 0.1)
+  signguard-hi: float > 0           (signguard: ... up to hi times the median norm, default 3.0; lo <= hi)
   pre-agg: none | nnm | bucketing   (pre-aggregation in front of the rule of ``server.mode``, docs/PARITY.md; default
                                     none.  nnm: every row becomes the mean of its n - f nearest rows, itself included
                                     (f from byz-f, needs n >= 2 f + 3 when explicit); bucketing: the rows are shuffled
@@ -86,7 +91,7 @@ from typing import Any, Dict, List, Optional
 import yaml
 
 SERVER_MODES = ("fedavg", "hyper", "FLTrust", "trimmed_mean", "shieldfl", "gmm", "krum", "median", "scionfl",
-                "fltracer", "byzantine", "multi_krum", "bulyan", "geomed", "dnc", "cclip", "foolsgold")
+                "fltracer", "byzantine", "multi_krum", "bulyan", "geomed", "dnc", "cclip", "foolsgold", "signguard")
 ATTACK_MODES = ("Random", "Min-Max", "Min-Sum", "Opt-Fang", "LIE", "AGR-Krum", "AGR-MKrum", "AGR-Bulyan")
 # the AGR-tailored attacks (beyond the reference; docs/PARITY.md) and the rule each one models
 AGR_ATTACK_TARGETS = {"AGR-Krum": "krum", "AGR-MKrum": "mkrum", "AGR-Bulyan": "bulyan"}
@@ -193,6 +198,12 @@ PRE_AGG_REFUSED_MODES = ("fedavg", "hyper", "FLTrust", "gmm", "foolsgold")
 BUCKET_SIZE = RuleKnob("bucket-size", "bucket_size", "int", 2, 1)
 # foolsgold is stateful and lives outside agg.AGGREGATORS: its knob is not a keyword every rule receives either
 FOOLSGOLD_KAPPA = RuleKnob("foolsgold-kappa", "foolsgold_kappa", "number", 1.0)
+# signguard's knobs reach its rule through its own server mode (fl/server_modes.py SignGuardMode), not through the
+# keywords every rule receives
+SIGNGUARD_FRAC = RuleKnob("signguard-frac", "signguard_frac", "number", 0.1)
+SIGNGUARD_LO = RuleKnob("signguard-lo", "signguard_lo", "number", 0.1)
+SIGNGUARD_HI = RuleKnob("signguard-hi", "signguard_hi", "number", 3.0)
+SIGNGUARD_KNOBS = (SIGNGUARD_FRAC, SIGNGUARD_LO, SIGNGUARD_HI)
 
 EXTENSION_DEFAULTS: Dict[str, Any] = {
     "comm": {"backend": "auto", "address": "", "port": 29517, "clients-per-rank": 0, "one-shot-allgather": "auto",
@@ -204,7 +215,7 @@ EXTENSION_DEFAULTS: Dict[str, Any] = {
                "phase-sync": False, "fault-inject": [], "save-state": False, "resume": False,
                "speculative": True, "compat-har-train": False, "compat-fedavg-alias": False,
                **{k.key: k.default for k in RULE_KNOBS}, "pre-agg": "none", BUCKET_SIZE.key: BUCKET_SIZE.default,
-               FOOLSGOLD_KAPPA.key: FOOLSGOLD_KAPPA.default},
+               FOOLSGOLD_KAPPA.key: FOOLSGOLD_KAPPA.default, **{k.key: k.default for k in SIGNGUARD_KNOBS}},
 }
 
 
@@ -374,6 +385,9 @@ class Config:
             raise ValueError(f"engine.pre-agg must be one of {PRE_AGG_KINDS} (got {pre!r})")
         BUCKET_SIZE.check(self.engine.get(BUCKET_SIZE.key, BUCKET_SIZE.default), "engine.")
         FOOLSGOLD_KAPPA.check(self.engine.get(FOOLSGOLD_KAPPA.key, FOOLSGOLD_KAPPA.default), "engine.")
+        sg = [k.check(self.engine.get(k.key, k.default), "engine.") for k in SIGNGUARD_KNOBS]
+        if float(sg[1]) > float(sg[2]):
+            raise ValueError(f"engine.signguard-lo must be <= engine.signguard-hi (got {sg[1]!r}, {sg[2]!r})")
         if pre != "none" and self.mode in PRE_AGG_REFUSED_MODES:
             raise ValueError(f"engine.pre-agg: {pre} does not apply to server.mode '{self.mode}' (it goes in front of "
                              f"a robust rule; not {', '.join(PRE_AGG_REFUSED_MODES)})")

@@ -16,7 +16,7 @@ import torch
 from .. import ops
 from ..agg import AGGREGATORS, AggResult, pre_aggregate
 from ..agg import foolsgold as agg_foolsgold
-from ..config import FOOLSGOLD_KAPPA
+from ..config import FOOLSGOLD_KAPPA, SIGNGUARD_KNOBS
 from ..data import DeviceTable, resolve_dataset
 from ..detect import HyperDetector
 from ..models import build_model
@@ -101,6 +101,10 @@ class RuleMode(ServerMode):
         # (gmm runs on the device without a host read up to 64 rows; its success is a device bool)
         return super().early_ok() and not (self.name == "gmm" and len(self.eng.selected) > 64)
 
+    def _args(self) -> dict:
+        """The keywords the rule is called with."""
+        return self.eng._rule_args()
+
     def step(self, U, sizes, attackers, ok_all, w=None, gen_key=None):
         eng = self.eng
         g_old = eng.global_params
@@ -113,7 +117,7 @@ class RuleMode(ServerMode):
             else:
                 eng.global_params = torch.where(ok_all, ops.weighted_rows(U, w), g_old)
             return {"n": int(U.shape[0])}, None
-        args, pre = eng._rule_args(), None
+        args, pre = self._args(), None
         if eng.cfg.engine.get("pre-agg", "none") != "none":
             # (device work without a host read, like the rules: the rule then sees the mixed rows and their sizes)
             U, sizes, pre = pre_aggregate(eng.cfg.engine["pre-agg"], U, sizes, byz_f=args["byz_f"], seed=args["seed"],
@@ -136,6 +140,18 @@ class RuleMode(ServerMode):
             eng.global_params = torch.where(ok_all if rule_ok is None else ok_all & rule_ok,
                                             res.params.to(torch.float32), g_old)
         return info, rule_ok
+
+
+class SignGuardMode(RuleMode):
+    """SignGuard: a stateless rule of ``AGGREGATORS`` whose three knobs are its own, not keywords of every rule."""
+
+    def early_ok(self) -> bool:
+        # (beyond the kernel's 64 rows the rule is its host mirror, which reads the statistics back)
+        return super().early_ok() and len(self.eng.selected) <= 64
+
+    def _args(self) -> dict:
+        e = self.eng.cfg.engine
+        return {**super()._args(), **{k.kw: k.check(e.get(k.key, k.default), coerce=True) for k in SIGNGUARD_KNOBS}}
 
 
 class FLTrustMode(ServerMode):
@@ -407,4 +423,4 @@ class HyperMode(ServerMode):
 
 
 MODES = {**{name: RuleMode for name in AGGREGATORS}, "hyper": HyperMode, "FLTrust": FLTrustMode,
-         "foolsgold": FoolsGoldMode}
+         "foolsgold": FoolsGoldMode, "signguard": SignGuardMode}

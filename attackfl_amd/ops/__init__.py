@@ -521,6 +521,65 @@ def dnc_filter(U: torch.Tensor, b: int, iters: int, seed: int, drop: int, w: tor
     return composite.dnc_select(composite.dnc_gram(U, int(b), int(iters), seed), int(drop), w)
 
 
+def _sg_native(t: torch.Tensor, n: int) -> bool:
+    return _dev(t) and 1 <= n <= 64
+
+
+def _sg_out(out):
+    keep, ok, label, F, c, info = out[:6]
+    return keep.bool(), ok.bool(), label.to(torch.int64), F, c, info[0], info[1]
+
+
+def signguard_window(P: int, frac: float, seed: int, native_mix: bool = False):
+    """SignGuard's sampled window (s, b) of (seed, P) (``composite.signguard_window``); ``native_mix``: s from the
+    native twin of the mixer (plan_perm.h ``pl_signguard_start``), which the device path uses."""
+    s, b = composite.signguard_window(P, frac, seed)
+    if native_mix and b < int(P):
+        s = int(native().signguard_start(_seed64(seed), int(P)))
+    return s, b
+
+
+def sign_stats(U: torch.Tensor, g: torch.Tensor, s: int, b: int):
+    """SignGuard's row statistics about the centre g -> (q [n] fp64 squared norms of U - g, pos [n], neg [n] int64 sign
+    counts on the window (s, b)).  Device, n <= 64: ``k_sign_stats``, one pass over U and g, its block partials summed
+    in block order by ``k_signguard_select``: this call runs both launches of ``signguard_filter`` (with equal weights
+    and lo = hi = 1) and returns the statistics the second one summed, so it costs what ``signguard_filter`` costs and
+    is there for tests and tools, not for a round.  A non-contiguous view is made contiguous first."""
+    if _sg_native(U, U.shape[0]):
+        one = torch.ones(U.shape[0], dtype=torch.float64, device=U.device)
+        out = native().signguard_run(U.to(torch.float32).contiguous(),
+                                     g.to(device=U.device, dtype=torch.float32).contiguous(), int(s), int(b), one,
+                                     1.0, 1.0)
+        return out[6], out[7][:, 0].to(torch.int64), out[7][:, 1].to(torch.int64)
+    return composite.sign_stats(U, g, int(s), int(b))
+
+
+def signguard_select(q: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, b: int, alpha: torch.Tensor, lo: float,
+                     hi: float):
+    """SignGuard's decisions from the row statistics -> (keep [n] bool, norm_ok [n] bool, label [n] int64, features
+    [n, 3] fp64, c [n] fp64, M, h), the last two 0-d fp64.  Device, n <= 64: ``k_signguard_select`` (one launch, no
+    host read); otherwise the host mirror, which reads the statistics back."""
+    if _sg_native(q, q.numel()):
+        i32 = lambda t: t.to(device=q.device, dtype=torch.int32).contiguous()
+        return _sg_out(native().signguard_select(q.to(torch.float64).contiguous(), i32(pos), i32(neg), int(b),
+                                                 alpha.to(device=q.device, dtype=torch.float64).contiguous(),
+                                                 float(lo), float(hi)))
+    return composite.signguard_select(q, pos, neg, int(b), alpha, float(lo), float(hi))[:7]
+
+
+def signguard_filter(U: torch.Tensor, g: torch.Tensor, frac: float, seed: int, alpha: torch.Tensor, lo: float,
+                     hi: float):
+    """``signguard_select`` on ``sign_stats`` over the window of (frac, seed) -> its seven results, then the window
+    (s, b).  Device, n <= 64: two launches (``k_sign_stats``, ``k_signguard_select``), no host read."""
+    if _sg_native(U, U.shape[0]):
+        s, b = signguard_window(U.shape[1], frac, seed, native_mix=True)
+        out = native().signguard_run(U.to(torch.float32).contiguous(),
+                                     g.to(device=U.device, dtype=torch.float32).contiguous(), s, b,
+                                     alpha.to(device=U.device, dtype=torch.float64).contiguous(), float(lo), float(hi))
+        return _sg_out(out) + ((s, b),)
+    return composite.signguard_filter(U, g, frac, seed, alpha.to(U.device), float(lo), float(hi))
+
+
 def row_norms(U: torch.Tensor) -> torch.Tensor:
     if _dev(U):
         return native().row_dots(U.contiguous(), U.new_zeros(0), 0)[:, 0].clamp_min(0).sqrt()

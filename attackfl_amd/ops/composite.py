@@ -817,3 +817,156 @@ def dnc_select(G: torch.Tensor, drop: int, w: torch.Tensor, centre: bool = False
     keep = torch.where(keep.any(), keep, torch.ones_like(keep))
     wk = w.to(device=G.device, dtype=torch.float64) * keep.double()
     return keep, s, wk / wk.sum()
+
+
+# ---------------------------------------------------------------- SignGuard (docs/PARITY.md)
+def signguard_mix(seed: int) -> int:
+    """The 32-bit word the window's first column comes from (mirror of plan_perm.h ``pl_signguard_mix``; the one place
+    the derivation is written down on the Python side)."""
+    from ..fl.trainers import _M32, _mix_i
+
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    a, b = _mix_i((seed & _M32) ^ 0x5347D1A3), _mix_i((seed >> 32) ^ 0x6A09E667)
+    return _mix_i((a + 0x9E3779B9 * b) & _M32)
+
+
+def signguard_window(P: int, frac: float, seed: int):
+    """SignGuard's sampled columns as (s, b): the contiguous window s, s + 1, ..., s + b - 1 taken mod P, with
+    b = min(P, max(1, ceil(frac P))) and s = mix(seed) mod P; all columns (b = P) start at s = 0."""
+    P, frac = int(P), float(frac)
+    if P < 1 or not frac > 0.0:
+        raise ValueError(f"signguard_window needs P >= 1 and frac > 0 (got {P}, {frac})")
+    b = P if frac >= 1.0 else min(P, max(1, math.ceil(frac * P)))
+    return (0, P) if b >= P else (signguard_mix(seed) % P, b)
+
+
+def sign_stats(U: torch.Tensor, g: torch.Tensor, s: int, b: int):
+    """SignGuard's per-row statistics about the centre g (``k_sign_stats``) -> (q [n] fp64 = sum_p d_ip^2 over all P
+    columns, pos [n], neg [n] int64 = the counts of d_ip > 0 and d_ip < 0 over the window (s, b)), d = U - g in fp64.
+    A NaN difference is neither positive nor negative; an infinite one counts by its sign."""
+    P, s, b = U.shape[1], int(s), int(b)
+    if P < 1 or not 1 <= b <= P or not 0 <= s < P:
+        raise ValueError(f"sign_stats needs 1 <= b <= P and 0 <= s < P (got s = {s}, b = {b}, P = {P})")
+    d = U.double() - g.to(device=U.device).double()[None, :]
+    q = (d * d).sum(dim=1)
+    dw = d.index_select(1, (s + torch.arange(b, device=U.device)) % P)
+    return q, (dw > 0).sum(dim=1), (dw < 0).sum(dim=1)
+
+
+def _sg_margin(x: float, y: float) -> float:
+    """The relative margin |x - y| / max(|x|, |y|) of a comparison between x and y (0 when they are equal, 1 against
+    an infinite side)."""
+    if x == y:
+        return 0.0
+    m = max(abs(x), abs(y))
+    return 1.0 if math.isinf(m) else abs(x - y) / m
+
+
+def _sg_d2(a, c) -> float:
+    """Squared distance in the feature plane, in the kernel's expression shape ((dx dx + dy dy) + dz dz)."""
+    dx, dy, dz = a[0] - c[0], a[1] - c[1], a[2] - c[2]
+    return (dx * dx + dy * dy) + dz * dz
+
+
+SIGNGUARD_MAX_ITER = 300
+
+
+def signguard_select(q: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, b: int, alpha: torch.Tensor, lo: float,
+                     hi: float):
+    """SignGuard's decisions from the rows' statistics (``k_signguard_select``; steps 3 to 5 of the rule text in
+    docs/PARITY.md): the norm filter about the lower median norm M, deterministic flat-kernel mean shift on the sign
+    features F = (pos, b - pos - neg, neg) / b with the bandwidth h, the largest cluster, and the clipped weights
+    c_i = keep_i alpha_i s_i / sum_kept alpha -> (keep [n] bool, norm_ok [n] bool, label [n] int64, F [n, 3] fp64,
+    c [n] fp64, M, h (0-d fp64), margin).  Plain Python floats (IEEE fp64, no contraction) in the kernel's expression
+    shapes and summation orders: distances are compared squared, sums run in index order.  It reads its inputs back to
+    the host, so it serves any device and any n; the results go back to ``q``'s device.
+
+    ``margin`` (a float) is the smallest relative margin |x - y| / max(|x|, |y|) met by any comparison whose outcome a
+    rounding error could change: a finite norm against lo M and hi M, every squared distance against h^2 (the mean-shift
+    memberships and counts, the dedup), every squared move against (1e-3 h)^2, a row's nearest centre against its
+    second nearest, and the largest cluster's size against the runner-up's.  The counts that order the seeds are
+    integers, the same on both sides whenever the memberships are; a tie among them goes to the lower index and changes
+    the outcome only through a label or size tie, which is in the margin."""
+    dev = q.device
+    n, b, lo, hi = int(q.numel()), int(b), float(lo), float(hi)
+    if n < 1 or b < 1:
+        raise ValueError(f"signguard_select needs n >= 1 and b >= 1 (got {n}, {b}); lo <= hi is ``agg.signguard``'s check")
+    ql = q.detach().double().cpu().reshape(-1).tolist()
+    pl = [int(v) for v in pos.detach().cpu().reshape(-1).tolist()]
+    nl = [int(v) for v in neg.detach().cpu().reshape(-1).tolist()]
+    al = alpha.detach().double().cpu().reshape(-1).tolist()
+    margin = [1.0]
+
+    def le(x, y):  # x <= y, its margin recorded
+        margin[0] = min(margin[0], _sg_margin(x, y))
+        return x <= y
+
+    # 3. norm filter
+    inf = float("inf")
+    norm = [math.sqrt(v) if math.isfinite(v) else inf for v in ql]
+    M = sorted(norm)[(n - 1) // 2]
+    ok = [math.isfinite(v) and math.isfinite(M) and le(lo * M, v) and le(v, hi * M) for v in norm]
+    scale = [1.0 if v <= M else M / v for v in norm]
+    # 4. features and bandwidth
+    F = [(pl[i] / b, (b - pl[i] - nl[i]) / b, nl[i] / b) for i in range(n)]
+    k = max(1, int(0.5 * n))
+    rsum = 0.0
+    for i in range(n):
+        rsum += math.sqrt(sorted(_sg_d2(F[j], F[i]) for j in range(n))[k - 1])
+    h = max(rsum / n, 1.0 / b)
+    h2, tol = h * h, 1e-3 * h
+    conv2 = tol * tol
+    centres, cnt = [], []
+    for i in range(n):
+        c = F[i]
+        for _ in range(SIGNGUARD_MAX_ITER):
+            mem = [j for j in range(n) if le(_sg_d2(F[j], c), h2)]
+            if not mem:
+                break
+            s0 = s1 = s2 = 0.0
+            for j in mem:
+                s0, s1, s2 = s0 + F[j][0], s1 + F[j][1], s2 + F[j][2]
+            new = (s0 / len(mem), s1 / len(mem), s2 / len(mem))
+            mv2, c = _sg_d2(new, c), new
+            if le(mv2, conv2):
+                break
+        centres.append(c)
+        cnt.append(sum(1 for j in range(n) if le(_sg_d2(F[j], c), h2)))
+    # dedup, labels, the largest cluster
+    order = sorted(range(n), key=lambda i: (-cnt[i], i))
+    alive = [True] * n
+    for p, sp in enumerate(order):
+        if alive[sp]:
+            for sq in order[p + 1:]:
+                if alive[sq] and le(_sg_d2(centres[sq], centres[sp]), h2):
+                    alive[sq] = False
+    surv = [sp for sp in order if alive[sp]]
+    label = []
+    for i in range(n):
+        d = [_sg_d2(F[i], centres[sp]) for sp in surv]
+        best = min(range(len(surv)), key=lambda t: (d[t], t))
+        if len(surv) > 1:
+            margin[0] = min(margin[0], _sg_margin(d[best], min(v for t, v in enumerate(d) if t != best)))
+        label.append(best)
+    size = [sum(1 for v in label if v == t) for t in range(len(surv))]
+    top = min(range(len(surv)), key=lambda t: (-size[t], t))
+    if len(surv) > 1:
+        margin[0] = min(margin[0], _sg_margin(float(size[top]), float(max(v for t, v in enumerate(size) if t != top))))
+    # 5. weights
+    keep = [ok[i] and label[i] == top for i in range(n)]
+    den = 0.0
+    for i in range(n):
+        den += al[i] if keep[i] else 0.0
+    c = [(al[i] * scale[i]) / den if keep[i] else 0.0 for i in range(n)]
+    t64 = lambda v: torch.tensor(v, dtype=torch.float64, device=dev)
+    return (torch.tensor(keep, dtype=torch.bool, device=dev), torch.tensor(ok, dtype=torch.bool, device=dev),
+            torch.tensor(label, dtype=torch.int64, device=dev), t64(F).reshape(n, 3), t64(c), t64(M), t64(h), margin[0])
+
+
+def signguard_filter(U: torch.Tensor, g: torch.Tensor, frac: float, seed: int, alpha: torch.Tensor, lo: float,
+                     hi: float):
+    """``signguard_select`` on ``sign_stats`` over ``signguard_window`` -> its results without the margin, then the
+    window (s, b)."""
+    s, b = signguard_window(U.shape[1], frac, seed)
+    q, pos, neg = sign_stats(U, g, s, b)
+    return signguard_select(q, pos, neg, b, alpha, lo, hi)[:7] + ((s, b),)

@@ -179,6 +179,71 @@ std::vector<torch::Tensor> dnc_run(torch::Tensor src, int64_t b, int64_t iters, 
   return {keep, scores, weights, gout};
 }
 
+// SignGuard (agg.signguard; agg.hip k_sign_stats / k_signguard_select).  signguard_run: U [n <= 64, P] fp32, g [P] fp32,
+// the window (s, b), alpha [n] fp64 -> the statistics launch, then the select launch on its partials.
+// signguard_select: the select launch alone on given statistics q [n] fp64, pos / neg [n] int32 (one block's partials).
+// Both -> (keep, norm_ok [n] uint8, label [n] int32, features [n, 3], c [n], info [2] = {M, h}, q [n], counts [n, 2] int32)
+std::vector<torch::Tensor> signguard_finish(torch::Tensor partial, int nb, int64_t n, int64_t b, torch::Tensor alpha,
+                                            double lo, double hi) {
+  auto opt = alpha.options();  // (the kernel writes every element of every output)
+  auto keep = torch::empty({n}, opt.dtype(torch::kUInt8));
+  auto norm_ok = torch::empty({n}, opt.dtype(torch::kUInt8));
+  auto label = torch::empty({n}, opt.dtype(torch::kInt32));
+  auto feat = torch::empty({n, 3}, opt);
+  auto c = torch::empty({n}, opt);
+  auto info = torch::empty({2}, opt);
+  auto q = torch::empty({n}, opt);
+  auto counts = torch::empty({n, 2}, opt.dtype(torch::kInt32));
+  TORCH_CHECK(afl_signguard_select(partial.data_ptr<double>(), nb, (int)n, (long)b, alpha.data_ptr<double>(), lo, hi,
+                                   keep.data_ptr<uint8_t>(), norm_ok.data_ptr<uint8_t>(), label.data_ptr<int>(),
+                                   feat.data_ptr<double>(), c.data_ptr<double>(), info.data_ptr<double>(),
+                                   q.data_ptr<double>(), counts.data_ptr<int>(), cur()) == 0,
+              "signguard_select launch failed");
+  AFL_CHECK_LAUNCH();
+  return {keep, norm_ok, label, feat, c, info, q, counts};
+}
+
+void signguard_check(int64_t n, int64_t b, const torch::Tensor& alpha) {  // (lo, hi: the launcher's check)
+  check_dev(alpha, "alpha", torch::kFloat64);
+  TORCH_CHECK(alpha.numel() == n && b >= 1 && b <= (int64_t)INT_MAX, "signguard: alpha [n] and 1 <= b < 2^31 (got n = ",
+              n, ", ", alpha.numel(), " weights, b = ", b, ")");
+}
+
+std::vector<torch::Tensor> signguard_run(torch::Tensor U, torch::Tensor g, int64_t s, int64_t b, torch::Tensor alpha,
+                                         double lo, double hi) {
+  check_dev(U, "U", torch::kFloat32);
+  check_dev(g, "g", torch::kFloat32);
+  TORCH_CHECK(U.dim() == 2 && U.size(0) >= 1 && U.size(0) <= 64 && U.size(1) >= 1 && U.size(1) <= (int64_t)INT_MAX,
+              "signguard: U [n <= 64, P < 2^31]");
+  const int64_t n = U.size(0), P = U.size(1);
+  TORCH_CHECK(g.dim() == 1 && g.size(0) == P && g.device() == U.device() && alpha.device() == U.device(),
+              "signguard: g [P] and alpha on U's device (got ", g.numel(), " values for P = ", P, ")");
+  signguard_check(n, b, alpha);
+  TORCH_CHECK(b <= P && s >= 0 && s < P, "signguard: the window needs 1 <= b <= P and 0 <= s < P (got s = ", s, ", b = ",
+              b, ", P = ", P, ")");
+  const int nb = afl_sign_stats_nblocks(P);
+  auto partial = torch::empty({2 * (int64_t)nb * n}, alpha.options());
+  TORCH_CHECK(afl_sign_stats(U.data_ptr<float>(), g.data_ptr<float>(), (int)n, P, s, b, partial.data_ptr<double>(),
+                             cur()) == 0, "sign_stats launch failed");
+  return signguard_finish(partial, nb, n, b, alpha, lo, hi);
+}
+
+std::vector<torch::Tensor> signguard_select(torch::Tensor q, torch::Tensor pos, torch::Tensor neg, int64_t b,
+                                            torch::Tensor alpha, double lo, double hi) {
+  check_dev(q, "q", torch::kFloat64);
+  check_dev(pos, "pos", torch::kInt32);
+  check_dev(neg, "neg", torch::kInt32);
+  const int64_t n = q.numel();
+  TORCH_CHECK(n >= 1 && n <= 64 && pos.numel() == n && neg.numel() == n && pos.device() == q.device() &&
+                  neg.device() == q.device() && alpha.device() == q.device(),
+              "signguard_select: q, pos, neg, alpha [n <= 64] on one device");
+  signguard_check(n, b, alpha);
+  auto partial = torch::empty({2 * n}, q.options());
+  partial.narrow(0, 0, n).copy_(q.reshape({n}));
+  partial.narrow(0, n, n).view(torch::kInt32).view({n, 2}).copy_(torch::stack({pos.reshape({n}), neg.reshape({n})}, 1));
+  return signguard_finish(partial, 1, n, b, alpha, lo, hi);
+}
+
 // Krum selection (agg.multi_krum / agg.bulyan): D [n, n] fp64 -> (sel [rounds] int32 in selection order, mask [n]
 // uint8, first-pass scores [n] fp64)
 std::vector<torch::Tensor> krum_select(torch::Tensor D, int64_t f, int64_t rounds, bool iterated) {
@@ -1091,6 +1156,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nnm_weights", &nnm_weights);
   m.def("agr_bisect", &agr_bisect);
   m.def("dnc_run", &dnc_run);
+  m.def("signguard_run", &signguard_run);
+  m.def("signguard_select", &signguard_select);
+  m.def("signguard_start", [](int64_t seed, int64_t P) {
+    TORCH_CHECK(P >= 1 && P <= (int64_t)INT_MAX, "signguard_start: 1 <= P < 2^31");
+    return (int64_t)afl_signguard_start((uint64_t)seed, (long)P);
+  });
+  m.def("sign_stats_chunk", &afl_sign_stats_chunk);
+  m.def("sign_stats_nblocks", [](int64_t P) { return afl_sign_stats_nblocks((long)P); });
   m.def("bulyan_coord", &bulyan_coord);
   m.def("geomed_weights", &geomed_weights);
   m.def("gram_anchored", &gram_anchored);

@@ -514,6 +514,22 @@ long afl_dnc_partials(int K, long P, long b, int iters);
 int afl_dnc_gram(const float* U, int K, long P, long b, int iters, uint64_t seed, double* partial, hipStream_t s);
 int afl_dnc_select(const double* src, int nb, int n, int iters, int centre, int drop, const double* w,
                    unsigned char* keep, double* scores, double* weights, double* gout, hipStream_t s);
+// SignGuard (docs/PARITY.md) on U [K <= 64][P] fp32 about the centre g [P].  afl_sign_stats (agg.hip k_sign_stats): one
+// pass over U and g; per (column chunk, row) the fp64 squared norm of U - g over the chunk and the counts of positive
+// and negative differences over the chunk's columns of the window {s, ..., s + b - 1 mod P} -> partial,
+// 2 afl_sign_stats_nblocks(P) K doubles (the sums [nb][K], then the int32 counts [nb][K][2]).  Refused instead of
+// launched: K outside [1, 64], P < 1, b outside [1, P], s outside [0, P).  afl_signguard_select (k_signguard_select):
+// the partials of nb blocks summed in block order, then the norm filter about the lower median norm M (lo M <= norm <=
+// hi M), the mean-shift clustering of the sign features with bandwidth h and the clipped weights -> keep, norm_ok [n]
+// 0/1, label [n], feat [n][3], c [n] (the weights of afl_anchored_rows), info = {M, h}, qout [n], cout [n][2] the summed
+// statistics.  afl_signguard_start: the window's first column, pl_signguard_start (plan_perm.h), on the host.
+int afl_sign_stats_chunk();
+int afl_sign_stats_nblocks(long P);
+uint32_t afl_signguard_start(uint64_t seed, long P);
+int afl_sign_stats(const float* U, const float* g, int K, long P, long s, long b, double* partial, hipStream_t st);
+int afl_signguard_select(const double* part, int nb, int n, long b, const double* alpha, double lo, double hi,
+                         unsigned char* keep, unsigned char* norm_ok, int* label, double* feat, double* c, double* info,
+                         double* qout, int* cout, hipStream_t s);
 void afl_noise_philox(const float* own, float* out, long P, float sigma, uint64_t seed, hipStream_t s);
 
 // comm.hip — one-shot intra-node all-gather over IPC-mapped peer buffers (xGMI)

@@ -22,6 +22,8 @@
 //   foolsgold_weights  FoolsGold: cosines, pardoning and the logit weights from that Gram, one wave
 //   dnc_gram        DnC: fp64-MFMA Grams over keyed random column subsets, all iterations in one launch
 //   dnc_select      DnC: top eigenpair, scores, ranked drop, mask intersection and weights, one wave
+//   sign_stats      SignGuard: squared norms about the centre and sign counts on a column window, one pass
+//   signguard_select  SignGuard: norm filter, mean-shift clustering of the sign features and clipped weights, one wave
 // Shared: gram_for_tiles (the host's one T = 1 .. 4 launch of gram_f64, hist_gram and dnc_gram), gram_tile_mfma and
 // gram_block_partials (the tile body of gram_f64 and hist_gram, whose Grams must agree bit for bit) and lds_load_square
 // (the matrix load of geomed_weights, cclip_weights and foolsgold_weights).  The device code of gram_f64 and dnc_gram
@@ -1889,5 +1891,271 @@ __global__ void __launch_bounds__(64) k_foolsgold_weights(const double* __restri
 int afl_foolsgold_weights(const double* G, const double* alpha0, int n, double kappa, double* out, hipStream_t s) {
   if (n < 1 || n > GMM_MAXN || !(kappa > 0.0)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_foolsgold_weights, dim3(1), dim3(64), 0, s, G, alpha0, n, kappa, out);
+  return (int)hipGetLastError();
+}
+
+// ============================================================================ signguard
+// SignGuard (Xu, Huang, Qu & Song, ICDCS 2022; rule text in docs/PARITY.md) of n <= 64 rows about the centre g.
+// k_sign_stats: one pass over U and g.  Block (x, y) owns the columns [x SS_CH, (x + 1) SS_CH) of the rows
+// [y SS_ROWS, (y + 1) SS_ROWS); column p is in the sampled window {s, ..., s + b - 1 mod P} when p >= s ? p < e1 :
+// p < wrap (e1 = s + b, wrap = s + b - P: two integer compares).  The loads of the block's rows are issued together,
+// then per (block, row): qpart [x][row] = sum (U - g)^2 over the chunk in fp64 — every thread its SS_CH / 256 strided
+// columns in ascending order, an xor butterfly over the wave, the four waves in wave order — and cpart [x][row] =
+// {#(d > 0), #(d < 0)} over the chunk's window columns (a NaN difference is neither).  No atomics; k_signguard_select
+// sums the blocks in block order.
+constexpr int SS_CH = 1024, SS_ROWS = 8;
+
+__global__ void __launch_bounds__(256) k_sign_stats(const float* __restrict__ U, const float* __restrict__ g, int K,
+                                                    long P, long s, long e1, long wrap, double* __restrict__ qpart,
+                                                    int* __restrict__ cpart) {
+  __shared__ double sq[SS_ROWS][4];
+  __shared__ int sc[SS_ROWS][4];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int r0 = blockIdx.y * SS_ROWS, nr = K - r0 < SS_ROWS ? K - r0 : SS_ROWS;
+  constexpr int M = SS_CH / 256;
+  double gv[M];
+  bool ok[M], win[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const long p = (long)blockIdx.x * SS_CH + t + 256 * m;
+    ok[m] = p < P;
+    gv[m] = ok[m] ? (double)g[p] : 0.0;
+    win[m] = ok[m] && (p >= s ? p < e1 : p < wrap);
+  }
+  float uv[SS_ROWS][M];
+#pragma unroll
+  for (int r = 0; r < SS_ROWS; ++r) {
+    const float* u = U + (long)(r0 + r) * P + (long)blockIdx.x * SS_CH + t;
+#pragma unroll
+    for (int m = 0; m < M; ++m) uv[r][m] = r < nr && ok[m] ? u[256 * m] : 0.0f;
+  }
+#pragma unroll
+  for (int r = 0; r < SS_ROWS; ++r) {
+    double q = 0.0;
+    int cnt = 0;  // pos in the low half, neg in the high half (<= SS_CH each)
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      if (r < nr && ok[m]) {
+        const double d = (double)uv[r][m] - gv[m];
+        q += d * d;
+        if (win[m]) cnt += (d > 0.0 ? 1 : 0) + (d < 0.0 ? 1 << 16 : 0);
+      }
+    }
+    for (int o = 32; o; o >>= 1) {
+      q += __shfl_xor(q, o, 64);
+      cnt += __shfl_xor(cnt, o, 64);
+    }
+    if (lane == 0) {
+      sq[r][w] = q;
+      sc[r][w] = cnt;
+    }
+  }
+  __syncthreads();
+  if (t < nr) {
+    const long e = (long)blockIdx.x * K + r0 + t;
+    qpart[e] = ((sq[t][0] + sq[t][1]) + sq[t][2]) + sq[t][3];
+    const int cnt = sc[t][0] + sc[t][1] + sc[t][2] + sc[t][3];
+    cpart[2 * e] = cnt & 0xFFFF;
+    cpart[2 * e + 1] = cnt >> 16;
+  }
+}
+
+int afl_sign_stats_chunk() { return SS_CH; }
+int afl_sign_stats_nblocks(long P) { return (int)afl_cdiv(P, SS_CH); }
+uint32_t afl_signguard_start(uint64_t seed, long P) { return pl_signguard_start(seed, (uint32_t)P); }
+
+// partial: 2 nb K doubles = qpart [nb][K] fp64, then cpart [nb][K][2] int32
+int afl_sign_stats(const float* U, const float* g, int K, long P, long s, long b, double* partial, hipStream_t st) {
+  if (K < 1 || K > GMM_MAXN || P < 1 || b < 1 || b > P || s < 0 || s >= P) return (int)hipErrorInvalidValue;
+  const int nb = afl_sign_stats_nblocks(P);
+  hipLaunchKernelGGL(k_sign_stats, dim3(nb, afl_cdiv(K, SS_ROWS)), dim3(256), 0, st, U, g, K, P, s, s + b, s + b - P,
+                     partial, (int*)(partial + (long)nb * K));
+  return (int)hipGetLastError();
+}
+
+// k_signguard_select: one wave, lane i owns row i; steps 2 to 5 of the rule.  part = the nb blocks' partials of
+// k_sign_stats (summed in block order; nb = 1: the statistics themselves).  Every comparison that decides something is
+// on fp64 values of the host mirror's expression shape (``composite.signguard_select``): contraction is off in this
+// kernel, distances are compared squared ((dx dx + dy dy) + dz dz against h h), sums run in index order.
+//   norms: q not finite -> +inf; M = the norm of rank (n - 1) / 2 by (norm, row); pass = finite and lo M <= norm <= hi M;
+//   scale = norm <= M ? 1 : M / norm.  F_i = (pos, b - pos - neg, neg) / b in LDS.
+//   h = max(mean_i sqrt(k-th smallest squared distance from F_i, itself counted), 1 / b), k = max(1, n / 2).
+//   mean shift from every row, flat kernel of radius h, <= SG_MAXIT moves, stop after a move of <= 1e-3 h (diverges per
+//   lane); cnt = points within h of the final centre; seeds ordered by (cnt descending, row); an alive seed removes the
+//   later seeds whose centres lie within h (one ballot per position); label = the nearest alive centre, the earlier one
+//   on a tie; the largest cluster, the earlier one on a tie; keep = pass and in it; c = keep alpha scale / sum kept alpha.
+// out: keep, norm_ok [n] 0/1, label [n], feat [n][3], c [n], info = {M, h}, qout [n], cout [n][2] = {pos, neg}.
+constexpr int SG_MAXIT = 300;
+
+__device__ __forceinline__ double sg_d2(double a0, double a1, double a2, double c0, double c1, double c2) {
+#pragma clang fp contract(off)
+  const double dx = a0 - c0, dy = a1 - c1, dz = a2 - c2;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
+__global__ void __launch_bounds__(64) k_signguard_select(const double* __restrict__ part, int nb, int n, long b,
+                                                         const double* __restrict__ alpha, double lo, double hi,
+                                                         unsigned char* __restrict__ keep,
+                                                         unsigned char* __restrict__ norm_ok, int* __restrict__ label,
+                                                         double* __restrict__ feat, double* __restrict__ c,
+                                                         double* __restrict__ info, double* __restrict__ qout,
+                                                         int* __restrict__ cout) {
+#pragma clang fp contract(off)
+  __shared__ double F[3][GMM_MAXN], C[3][GMM_MAXN], vec[GMM_MAXN], D[GMM_MAXN * KS_LD], Ms;
+  __shared__ int ord[GMM_MAXN], cn[GMM_MAXN];
+  const int i = threadIdx.x;
+  const bool act = i < n;
+  // ---- 2. statistics: the blocks in block order
+  double q = 0.0;
+  int pos = 0, neg = 0;
+  if (act) {
+    const int* cp = (const int*)(part + (long)nb * n);
+    for (int x = 0; x < nb; ++x) {
+      const long e = (long)x * n + i;
+      q += part[e];
+      pos += cp[2 * e];
+      neg += cp[2 * e + 1];
+    }
+  }
+  // ---- 3. norm filter
+  const double norm = act && gram_finite(q) ? sqrt(q) : INFINITY;
+  vec[i] = norm;
+  __syncthreads();
+  int rank = 0;
+  for (int l = 0; l < n; ++l) rank += (vec[l] < norm || (vec[l] == norm && l < i)) ? 1 : 0;
+  if (act && rank == (n - 1) / 2) Ms = norm;
+  __syncthreads();
+  const double M = Ms;
+  const bool pass = act && norm < INFINITY && lo * M <= norm && norm <= hi * M;
+  const double scale = norm <= M ? 1.0 : M / norm;
+  // ---- 4. features, bandwidth
+  const double bd = (double)b;
+  const double f0 = (double)pos / bd, f1 = (double)(b - pos - neg) / bd, f2 = (double)neg / bd;
+  F[0][i] = f0;
+  F[1][i] = f1;
+  F[2][i] = f2;
+  __syncthreads();
+  const int kth = n / 2 > 1 ? n / 2 : 1;
+  double r2 = 0.0;
+  if (act) {
+    double* row = D + i * KS_LD;
+    for (int j = 0; j < n; ++j) row[j] = sg_d2(F[0][j], F[1][j], F[2][j], f0, f1, f2);
+    for (int j = 0; j < n; ++j) {
+      const double dj = row[j];
+      int rk = 0;
+      for (int l = 0; l < n; ++l) rk += (row[l] < dj || (row[l] == dj && l < j)) ? 1 : 0;
+      if (rk == kth - 1) r2 = dj;
+    }
+  }
+  __syncthreads();  // (vec: every lane has read the norms)
+  vec[i] = sqrt(r2);
+  __syncthreads();
+  double rsum = 0.0;
+  for (int j = 0; j < n; ++j) rsum += vec[j];
+  const double rmean = rsum / (double)n, floor_h = 1.0 / bd;
+  const double h = rmean > floor_h ? rmean : floor_h;
+  const double h2 = h * h, tol = 1e-3 * h, conv2 = tol * tol;
+  // ---- mean shift: every row a seed
+  double c0 = f0, c1 = f1, c2 = f2;
+  int cnt = 0;
+  if (act) {
+    for (int it = 0; it < SG_MAXIT; ++it) {
+      double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+      int m = 0;
+      for (int j = 0; j < n; ++j) {
+        if (sg_d2(F[0][j], F[1][j], F[2][j], c0, c1, c2) <= h2) {
+          s0 += F[0][j];
+          s1 += F[1][j];
+          s2 += F[2][j];
+          ++m;
+        }
+      }
+      if (m == 0) break;
+      const double n0 = s0 / (double)m, n1 = s1 / (double)m, n2 = s2 / (double)m;
+      const double mv2 = sg_d2(n0, n1, n2, c0, c1, c2);
+      c0 = n0;
+      c1 = n1;
+      c2 = n2;
+      if (mv2 <= conv2) break;
+    }
+    for (int j = 0; j < n; ++j) cnt += sg_d2(F[0][j], F[1][j], F[2][j], c0, c1, c2) <= h2 ? 1 : 0;
+  }
+  C[0][i] = c0;
+  C[1][i] = c1;
+  C[2][i] = c2;
+  cn[i] = cnt;
+  __syncthreads();
+  // ---- dedup in the order (cnt descending, row ascending)
+  int mypos = 0;
+  for (int j = 0; j < n; ++j) mypos += (cn[j] > cnt || (cn[j] == cnt && j < i)) ? 1 : 0;
+  if (act) ord[mypos] = i;
+  __syncthreads();
+  unsigned long long alive = n == 64 ? ~0ull : (1ull << n) - 1ull;
+  for (int p = 0; p < n; ++p) {
+    const int sp = ord[p];
+    if ((alive >> sp) & 1ull) {  // (uniform)
+      const bool kill = act && mypos > p && ((alive >> i) & 1ull) &&
+                        sg_d2(c0, c1, c2, C[0][sp], C[1][sp], C[2][sp]) <= h2;
+      alive &= ~__ballot(kill);
+    }
+  }
+  // ---- labels: the nearest alive centre, the earlier one on a tie; the largest cluster
+  int lab = -1, ncl = 0;
+  double best = INFINITY;
+  for (int p = 0; p < n; ++p) {
+    const int sp = ord[p];
+    if ((alive >> sp) & 1ull) {
+      const double d2 = sg_d2(f0, f1, f2, C[0][sp], C[1][sp], C[2][sp]);
+      if (d2 < best) {
+        best = d2;
+        lab = ncl;
+      }
+      ++ncl;
+    }
+  }
+  __syncthreads();  // (cn: every lane has its position)
+  cn[i] = act ? lab : -1;
+  __syncthreads();
+  int top = 0, topsz = -1;
+  for (int cl = 0; cl < ncl; ++cl) {
+    int sz = 0;
+    for (int j = 0; j < n; ++j) sz += cn[j] == cl ? 1 : 0;
+    if (sz > topsz) {
+      topsz = sz;
+      top = cl;
+    }
+  }
+  // ---- 5. weights
+  const bool kp = pass && lab == top;
+  const double al = act ? alpha[i] : 0.0;
+  __syncthreads();  // (vec: every lane has summed the radii)
+  vec[i] = kp ? al : 0.0;
+  __syncthreads();
+  double den = 0.0;
+  for (int j = 0; j < n; ++j) den += vec[j];
+  if (act) {
+    keep[i] = kp ? 1 : 0;
+    norm_ok[i] = pass ? 1 : 0;
+    label[i] = lab;
+    feat[3 * i] = f0;
+    feat[3 * i + 1] = f1;
+    feat[3 * i + 2] = f2;
+    c[i] = kp ? (al * scale) / den : 0.0;
+    qout[i] = q;
+    cout[2 * i] = pos;
+    cout[2 * i + 1] = neg;
+  }
+  if (i == 0) {
+    info[0] = M;
+    info[1] = h;
+  }
+}
+
+int afl_signguard_select(const double* part, int nb, int n, long b, const double* alpha, double lo, double hi,
+                         unsigned char* keep, unsigned char* norm_ok, int* label, double* feat, double* c, double* info,
+                         double* qout, int* cout, hipStream_t s) {
+  if (n < 1 || n > GMM_MAXN || nb < 1 || b < 1 || !(lo > 0.0) || !(hi >= lo)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_signguard_select, dim3(1), dim3(64), 0, s, part, nb, n, b, alpha, lo, hi, keep, norm_ok, label,
+                     feat, c, info, qout, cout);
   return (int)hipGetLastError();
 }

@@ -2,7 +2,7 @@
 // sub-sampling (agg.hip k_dnc_gram).  6-round balanced Feistel network on the smallest even bit-width domain covering
 // n, with cycle walking back into [0, n).  __host__ __device__, so csrc/host/host_check.hip runs the same code under
 // ASan/UBSan on the CPU; mirrored bit-for-bit by attackfl_amd/fl/trainers.py (_mix_i, _perm_t, _half_bits) and
-// attackfl_amd/ops/composite.py (dnc_keys, dnc_columns).
+// attackfl_amd/ops/composite.py (dnc_keys, dnc_columns, signguard_mix).
 #pragma once
 #include <cstdint>
 #include <hip/hip_runtime.h>
@@ -54,4 +54,15 @@ __host__ __device__ __forceinline__ DncKeys pl_dnc_keys(uint64_t seed, int t) {
   k.k0 = pl_mix(a ^ (0x165667B1u * (uint32_t)(t + 1)));
   k.k1 = pl_mix(b + 0xD3A2646Cu * (uint32_t)(t + 1));
   return k;
+}
+
+// SignGuard (docs/PARITY.md): the first column s of the round's contiguous sampled window {s, ..., s + b - 1 mod P}
+// from the round's 64-bit seed, s = mix(seed) mod P (the caller takes s = 0 when the window is all P columns) — the one
+// place the derivation is written down on the native side.
+__host__ __device__ __forceinline__ uint32_t pl_signguard_mix(uint64_t seed) {
+  const uint32_t a = pl_mix((uint32_t)seed ^ 0x5347D1A3u), b = pl_mix((uint32_t)(seed >> 32) ^ 0x6A09E667u);
+  return pl_mix(a + 0x9E3779B9u * b);
+}
+__host__ __device__ __forceinline__ uint32_t pl_signguard_start(uint64_t seed, uint32_t P) {
+  return pl_signguard_mix(seed) % P;
 }

@@ -98,6 +98,11 @@ def run_cell(mode: str, attack: str, device: str, rounds: int, threads: int = 0,
             # foolsgold: every client's weight, averaged over the successful rounds that had a history, and the last one
             **({"alpha_mean": [round(sum(r["alpha"][i] for r in ok[1:]) / max(1, len(ok) - 1), 4) for i in range(8)],
                 "alpha_last": [round(a, 4) for a in ok[-1]["alpha"]]} if ok and "alpha" in ok[-1] else {}),
+            # the filtering rules (signguard: kept; dnc, multi_krum, bulyan: selected): per successful round the
+            # attackers the rule kept, and how many rows it kept in all
+            **({"attackers_kept": [[c for c in who if c in r[k]] for r in ok for k in ("kept", "selected") if k in r],
+                "rows_kept": [len(r[k]) for r in ok for k in ("kept", "selected") if k in r]}
+               if ok and any(k in ok[-1] and isinstance(ok[-1][k], list) for k in ("kept", "selected")) else {}),
             "seconds": round(time.time() - t0, 2)}
 
 
