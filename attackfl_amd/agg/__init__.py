@@ -17,7 +17,9 @@ Each rule returns ``AggResult(params [P] | None, ok, info)``.  Rows are in clien
 * byzantine     ``src/Utils.py:218-248`` (dead code in the reference) cosine ≥ 0.9 to model 0
 Beyond the reference (docs/PARITY.md): multi_krum, bulyan, dnc (assumed Byzantine count ``byz-f``), geomed (RFA) and
 cclip (centred clipping about the global model the round started from) and signguard (SignGuard: a norm filter about the
-median norm and a mean-shift clustering of the rows' sign statistics); the last two are the rules that take ``centre``.
+median norm and a mean-shift clustering of the rows' sign statistics) and flame (FLAME: the majority cluster of the
+updates' cosine distances, clipping to the median norm, Gaussian noise); the last three are the rules that take
+``centre``.
 Pre-aggregation in front of a rule (engine ``pre-agg``): ``nnm`` (nearest-neighbour mixing) and ``bucketing``.
 ``foolsgold`` (FoolsGold) is the one stateful rule: it takes and returns the clients' update history, so it is called by
 name (``fl/server_modes.py`` ``FoolsGoldMode``) and is not an entry of AGGREGATORS, the table of stateless rules.
@@ -33,7 +35,7 @@ import torch
 
 from .. import ops
 from ..config import BUCKET_SIZE, FOOLSGOLD_KAPPA, KNOB, PRE_AGG_KINDS  # (a knob's default and check: stated once, in config)
-from ..config import SIGNGUARD_FRAC, SIGNGUARD_HI, SIGNGUARD_LO
+from ..config import FLAME_NOISE, SIGNGUARD_FRAC, SIGNGUARD_HI, SIGNGUARD_LO
 from ..ops.composite import gmm_filter_ref  # noqa: F401  (the kernel's host mirror: tools and tests import it here)
 
 
@@ -272,6 +274,35 @@ def signguard(U: torch.Tensor, sizes=None, centre: Optional[torch.Tensor] = None
                       "bandwidth": h, "window": [s, b]})
 
 
+def flame(U: torch.Tensor, sizes=None, centre: Optional[torch.Tensor] = None, seed: int = 0,
+          flame_noise=FLAME_NOISE.default, **_) -> AggResult:
+    """FLAME (Nguyen et al., USENIX Security 2022; beyond the reference, rule text in docs/PARITY.md) about ``centre``
+    g, the global model the round started from: the rows kept are the majority cluster of the updates' cosine
+    distances (the first connected component of >= n' // 2 + 1 of the n' finite rows as the distance threshold grows:
+    HDBSCAN with min_cluster_size = n // 2 + 1, min_samples = 1, allow_single_cluster), each clipped to the lower
+    median S of all finite rows' norms, c_i = alpha_i min(1, S / ||x_i - g||) / sum_kept alpha, alpha = sizes / sum
+    sizes, and the result is g + sum_i c_i (x_i - g) + sigma z with sigma = ``flame_noise`` S and z the Philox normals
+    keyed by ``seed`` (``flame_noise`` 0: no noise); g itself when no row is finite.  Device, n <= 64: four launches
+    (``k_gram_f64``, ``k_gram_reduce``, ``k_flame_select``, ``k_flame_rows``), no host read.  Without a centre the
+    result is FedAvg, every row kept, no noise.  info = {kept, weights, median_norm, sigma, threshold, majority}.
+    Always a new tensor."""
+    n = U.shape[0]
+    lam = FLAME_NOISE.check(flame_noise, coerce=True)
+    a = _device_weights(sizes, U.device, n)
+    alpha = a / a.sum()
+    if centre is None:
+        zero = torch.zeros((), dtype=torch.float64, device=U.device)
+        return AggResult(ops.fedavg(U, a if sizes is None else sizes), True,
+                         {"kept": torch.ones(n, dtype=torch.bool, device=U.device), "weights": alpha,
+                          "median_norm": zero, "sigma": zero.clone(), "threshold": zero.clone(),
+                          "majority": torch.full((), n // 2 + 1, dtype=torch.int64, device=U.device)})
+    g = centre.to(device=U.device, dtype=torch.float32)
+    keep, c, info = ops.flame_filter(U, g, alpha, lam)
+    return AggResult(ops.flame_rows(U, c, g, info[1:2], seed), True,
+                     {"kept": keep, "weights": c, "median_norm": info[0], "sigma": info[1], "threshold": info[2],
+                      "majority": info[3].to(torch.int64)})
+
+
 def shieldfl(U: torch.Tensor, sizes=None, **_) -> AggResult:
     norms = ops.row_norms(U).to(U.device)
     Un = U / (norms.to(U.dtype)[:, None] + 1e-8)
@@ -419,6 +450,7 @@ AGGREGATORS = {
     "dnc": dnc,
     "cclip": cclip,
     "signguard": signguard,
+    "flame": flame,
     "shieldfl": shieldfl,
     "gmm": gmm,
     "scionfl": scionfl,

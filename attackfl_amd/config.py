@@ -24,11 +24,12 @@ Extensions (all optional, defaults keep reference behaviour):
   synthetic: auto | true | false   (auto = use the reference pickles when present)
   train-size / test-size / seed / har-train-size / har-test-size
 ``server:``
-  mode: the reference's modes plus multi_krum | bulyan | geomed | dnc | cclip | foolsgold | signguard (Multi-Krum,
-        Bulyan, the geometric median / RFA, Divide-and-Conquer and centred clipping: defences that assume f >= 1
+  mode: the reference's modes plus multi_krum | bulyan | geomed | dnc | cclip | foolsgold | signguard | flame
+        (Multi-Krum, Bulyan, the geometric median / RFA, Divide-and-Conquer and centred clipping: defences that assume f >= 1
         Byzantine clients; ``krum`` keeps the reference's f = 0, A-11; FoolsGold: the one rule with memory across rounds,
         a per-client history of updates whose cosines weigh colluders down; SignGuard: a norm filter about the median
-        norm and a clustering of the updates' sign statistics; definitions in docs/PARITY.md)
+        norm and a clustering of the updates' sign statistics; FLAME: the majority cluster of the updates' cosine
+        distances, clipping to the median norm and Gaussian noise; definitions in docs/PARITY.md)
 ``engine:``
   trainer: auto | fused | graph | eager | oracle  (fused = HIP persistent TransformerModel / RNNModel
                                     kernels; graph = HIP-graph-replayed layer programs for CNN/RNN/HAR models;
@@ -70,6 +71,8 @@ Extensions (all optional, defaults keep reference behaviour):
                                     window placed by the round's seed, default 0.1; >= 1 = every column)
   signguard-lo: float > 0           (signguard: a row passes the norm filter from lo times the median norm, default 0.1)
   signguard-hi: float > 0           (signguard: ... up to hi times the median norm, default 3.0; lo <= hi)
+  flame-noise: float >= 0           (flame: the noise level lambda, sigma = lambda times the median norm of the round's
+                                    updates, default 0.001, the paper's value for its main tasks; 0 = no noise)
   pre-agg: none | nnm | bucketing   (pre-aggregation in front of the rule of ``server.mode``, docs/PARITY.md; default
                                     none.  nnm: every row becomes the mean of its n - f nearest rows, itself included
                                     (f from byz-f, needs n >= 2 f + 3 when explicit); bucketing: the rows are shuffled
@@ -91,7 +94,8 @@ from typing import Any, Dict, List, Optional
 import yaml
 
 SERVER_MODES = ("fedavg", "hyper", "FLTrust", "trimmed_mean", "shieldfl", "gmm", "krum", "median", "scionfl",
-                "fltracer", "byzantine", "multi_krum", "bulyan", "geomed", "dnc", "cclip", "foolsgold", "signguard")
+                "fltracer", "byzantine", "multi_krum", "bulyan", "geomed", "dnc", "cclip", "foolsgold", "signguard",
+                "flame")
 ATTACK_MODES = ("Random", "Min-Max", "Min-Sum", "Opt-Fang", "LIE", "AGR-Krum", "AGR-MKrum", "AGR-Bulyan")
 # the AGR-tailored attacks (beyond the reference; docs/PARITY.md) and the rule each one models
 AGR_ATTACK_TARGETS = {"AGR-Krum": "krum", "AGR-MKrum": "mkrum", "AGR-Bulyan": "bulyan"}
@@ -145,7 +149,8 @@ REFERENCE_DEFAULTS: Dict[str, Any] = {
 @dataclass(frozen=True)
 class RuleKnob:
     """One engine knob of a server rule: the ``engine:`` key, the keyword the rule receives, what it holds (``kind``
-    "int" >= ``lo``, unchecked when ``lo`` is None, or "number" > 0; ``auto``: or the string "auto") and the default.
+    "int" >= ``lo``, unchecked when ``lo`` is None, "number" > 0, or "number0" >= 0 and finite; ``auto``: or the string
+    "auto") and the default.
     Stated once, in RULE_KNOBS: the engine defaults, ``validate``, ``FLEngine._rule_args`` and the rules (``agg``)
     read it."""
     key: str
@@ -157,8 +162,8 @@ class RuleKnob:
 
     def check(self, v, where: str = "", coerce: bool = False):
         """-> ``v`` when admissible, else ValueError.  A bool never is; a string only as a "number" (YAML 1.1 reads
-        "1e-6", without a dot, as a string); NaN is not > 0.  ``coerce`` (the engine's keywords, a rule's own
-        arguments): None counts as "auto", any other value goes through ``int`` / ``float`` first."""
+        "1e-6", without a dot, as a string); NaN is neither > 0 nor >= 0.  ``coerce`` (the engine's keywords, a rule's
+        own arguments): None counts as "auto", any other value goes through ``int`` / ``float`` first."""
         if self.auto and ((isinstance(v, str) and v == "auto") or (coerce and v is None)):
             return "auto"
         if coerce:
@@ -167,11 +172,13 @@ class RuleKnob:
             return v
         try:
             ok = not isinstance(v, bool) and ((isinstance(v, int) and v >= self.lo) if self.kind == "int"
-                                              else float(v) > 0)
+                                              else float(v) > 0 if self.kind == "number"
+                                              else 0 <= float(v) < float("inf"))
         except (TypeError, ValueError):
             ok = False
         if not ok:
-            what = f"an integer >= {self.lo}" if self.kind == "int" else "a number > 0"
+            what = (f"an integer >= {self.lo}" if self.kind == "int" else "a number > 0" if self.kind == "number"
+                    else "a finite number >= 0")
             what = "'auto' or " + what if self.auto else what
             raise ValueError(f"{where}{self.key} must be {what} (got {v!r})")
         return v
@@ -204,6 +211,8 @@ SIGNGUARD_FRAC = RuleKnob("signguard-frac", "signguard_frac", "number", 0.1)
 SIGNGUARD_LO = RuleKnob("signguard-lo", "signguard_lo", "number", 0.1)
 SIGNGUARD_HI = RuleKnob("signguard-hi", "signguard_hi", "number", 3.0)
 SIGNGUARD_KNOBS = (SIGNGUARD_FRAC, SIGNGUARD_LO, SIGNGUARD_HI)
+# flame's knob, likewise through its own server mode (FlameMode): the noise level lambda, 0 = no noise
+FLAME_NOISE = RuleKnob("flame-noise", "flame_noise", "number0", 0.001)
 
 EXTENSION_DEFAULTS: Dict[str, Any] = {
     "comm": {"backend": "auto", "address": "", "port": 29517, "clients-per-rank": 0, "one-shot-allgather": "auto",
@@ -215,7 +224,8 @@ EXTENSION_DEFAULTS: Dict[str, Any] = {
                "phase-sync": False, "fault-inject": [], "save-state": False, "resume": False,
                "speculative": True, "compat-har-train": False, "compat-fedavg-alias": False,
                **{k.key: k.default for k in RULE_KNOBS}, "pre-agg": "none", BUCKET_SIZE.key: BUCKET_SIZE.default,
-               FOOLSGOLD_KAPPA.key: FOOLSGOLD_KAPPA.default, **{k.key: k.default for k in SIGNGUARD_KNOBS}},
+               FOOLSGOLD_KAPPA.key: FOOLSGOLD_KAPPA.default, **{k.key: k.default for k in SIGNGUARD_KNOBS},
+               FLAME_NOISE.key: FLAME_NOISE.default},
 }
 
 
@@ -388,6 +398,7 @@ class Config:
         sg = [k.check(self.engine.get(k.key, k.default), "engine.") for k in SIGNGUARD_KNOBS]
         if float(sg[1]) > float(sg[2]):
             raise ValueError(f"engine.signguard-lo must be <= engine.signguard-hi (got {sg[1]!r}, {sg[2]!r})")
+        FLAME_NOISE.check(self.engine.get(FLAME_NOISE.key, FLAME_NOISE.default), "engine.")
         if pre != "none" and self.mode in PRE_AGG_REFUSED_MODES:
             raise ValueError(f"engine.pre-agg: {pre} does not apply to server.mode '{self.mode}' (it goes in front of "
                              f"a robust rule; not {', '.join(PRE_AGG_REFUSED_MODES)})")

@@ -52,9 +52,9 @@ from .hyper_server import HyperServer
 from .server_modes import MODES, ServerMode
 from .trainers import Pending, Plan, make_plan, make_trainer
 
-# every rule of AGGREGATORS runs on the device without a host read (gmm and signguard up to 64 rows; gmm's success is a
-# device bool): with one of them the aggregate and the next round's launch are enqueued before the host waits for the
-# training, as for FedAvg, FLTrust and the native hypernetwork update (ServerMode.early_ok, FLEngine._early_launch)
+# every rule of AGGREGATORS runs on the device without a host read (gmm, signguard and flame up to 64 rows; gmm's
+# success is a device bool): with one of them the aggregate and the next round's launch are enqueued before the host
+# waits for the training, as for FedAvg, FLTrust and the native hypernetwork update (ServerMode.early_ok, FLEngine._early_launch)
 EARLY_AGGREGATORS = tuple(m for m in AGGREGATORS if m != "fedavg")
 
 META = 5  # valid, result, size, is_attacker, decision word; then the client's per-epoch losses (E columns)

@@ -16,7 +16,7 @@ import torch
 from .. import ops
 from ..agg import AGGREGATORS, AggResult, pre_aggregate
 from ..agg import foolsgold as agg_foolsgold
-from ..config import FOOLSGOLD_KAPPA, SIGNGUARD_KNOBS
+from ..config import FLAME_NOISE, FOOLSGOLD_KAPPA, SIGNGUARD_KNOBS
 from ..data import DeviceTable, resolve_dataset
 from ..detect import HyperDetector
 from ..models import build_model
@@ -152,6 +152,19 @@ class SignGuardMode(RuleMode):
     def _args(self) -> dict:
         e = self.eng.cfg.engine
         return {**super()._args(), **{k.kw: k.check(e.get(k.key, k.default), coerce=True) for k in SIGNGUARD_KNOBS}}
+
+
+class FlameMode(RuleMode):
+    """FLAME: a stateless rule of ``AGGREGATORS`` with a knob of its own (the noise level)."""
+
+    def early_ok(self) -> bool:
+        # (beyond the kernel's 64 rows the rule is its host mirror, which reads the Gram back)
+        return super().early_ok() and len(self.eng.selected) <= 64
+
+    def _args(self) -> dict:
+        e = self.eng.cfg.engine
+        return {**super()._args(), FLAME_NOISE.kw: FLAME_NOISE.check(e.get(FLAME_NOISE.key, FLAME_NOISE.default),
+                                                                     coerce=True)}
 
 
 class FLTrustMode(ServerMode):
@@ -423,4 +436,4 @@ class HyperMode(ServerMode):
 
 
 MODES = {**{name: RuleMode for name in AGGREGATORS}, "hyper": HyperMode, "FLTrust": FLTrustMode,
-         "foolsgold": FoolsGoldMode, "signguard": SignGuardMode}
+         "foolsgold": FoolsGoldMode, "signguard": SignGuardMode, "flame": FlameMode}

@@ -580,6 +580,37 @@ def signguard_filter(U: torch.Tensor, g: torch.Tensor, frac: float, seed: int, a
     return composite.signguard_filter(U, g, frac, seed, alpha.to(U.device), float(lo), float(hi))
 
 
+def flame_select(G: torch.Tensor, alpha: torch.Tensor, lam: float):
+    """FLAME's decisions from the Gram about the centre -> (keep [n] bool, c [n] fp64, info [5] fp64 = {S the lower
+    median norm, sigma = lam S, d* the threshold, m the majority, n' the finite rows}) on G's device.  Device, n <= 64:
+    ``k_flame_select`` (one launch, no host read); otherwise the host mirror, which reads G back."""
+    if _dev(G) and 1 <= G.shape[0] <= 64:
+        keep, c, info = native().flame_select(G.to(torch.float64).contiguous(),
+                                              alpha.to(device=G.device, dtype=torch.float64).contiguous(), float(lam))
+        return keep.bool(), c, info
+    return composite.flame_select(G, alpha, float(lam))[:3]
+
+
+def flame_filter(U: torch.Tensor, g: torch.Tensor, alpha: torch.Tensor, lam: float):
+    """``flame_select`` on ``gram_anchored(U, g)``.  Device, n <= 64: three launches (``k_gram_f64``, ``k_gram_reduce``,
+    ``k_flame_select``), no host read."""
+    return flame_select(gram_anchored(U, g), alpha, lam)
+
+
+def flame_rows(U: torch.Tensor, c: torch.Tensor, anchor: torch.Tensor, sigma, seed: int) -> torch.Tensor:
+    """anchor + sum_{j: c_j != 0} c_j (U_j - anchor) + sigma z, z the Philox normals under ``composite.flame_key(seed)``
+    (``k_flame_rows``: one pass over U; sigma, a number or a one-element fp64 tensor such as ``flame_select``'s
+    info[1:2], is read on the device).  sigma = 0: the bits of ``anchored_rows``."""
+    if _dev(U):
+        s = (sigma.to(device=U.device, dtype=torch.float64).reshape(-1) if torch.is_tensor(sigma)
+             else torch.full((1,), float(sigma), dtype=torch.float64, device=U.device))
+        return native().flame_rows(U.to(torch.float32).contiguous(),
+                                   c.to(device=U.device, dtype=torch.float64).contiguous(),
+                                   anchor.to(device=U.device, dtype=torch.float32).contiguous(), s,
+                                   _seed64(composite.flame_key(seed)))
+    return composite.flame_rows(U, c, anchor, sigma, seed)
+
+
 def row_norms(U: torch.Tensor) -> torch.Tensor:
     if _dev(U):
         return native().row_dots(U.contiguous(), U.new_zeros(0), 0)[:, 0].clamp_min(0).sqrt()

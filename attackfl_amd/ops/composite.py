@@ -970,3 +970,97 @@ def signguard_filter(U: torch.Tensor, g: torch.Tensor, frac: float, seed: int, a
     s, b = signguard_window(U.shape[1], frac, seed)
     q, pos, neg = sign_stats(U, g, s, b)
     return signguard_select(q, pos, neg, b, alpha, lo, hi)[:7] + ((s, b),)
+
+
+# ---------------------------------------------------------------- FLAME (docs/PARITY.md)
+def flame_key(seed: int) -> int:
+    """The 64-bit Philox key of FLAME's server-side noise from the round's seed (the one place the derivation is written
+    down: the native side takes the key).  The seed goes through the project's 32-bit mixer with constants of its own,
+    so the stream is neither the Random attack's (keyed by its seed itself) nor scionfl's."""
+    from ..fl.trainers import _M32, _mix_i
+
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    a, b = _mix_i((seed & _M32) ^ 0x464C414D), _mix_i((seed >> 32) ^ 0x3C6EF372)
+    return _mix_i((a + 0x9E3779B9 * b) & _M32) | (_mix_i((b + 0xC2B2AE35 * a + 1) & _M32) << 32)
+
+
+def flame_select(G: torch.Tensor, alpha: torch.Tensor, lam: float):
+    """FLAME's decisions from the Gram G [n, n] of the updates about the centre (``k_flame_select``; steps 1 to 4 of the
+    rule text in docs/PARITY.md, sigma of step 5) -> (keep [n] bool, c [n] fp64, info [5] fp64 = {S, sigma, d*, m, n'},
+    margin).  Finite rows are those with a finite G_ii (n' of them, m = n' // 2 + 1); D_ij = 1 - G_ij / (sqrt(G_ii)
+    sqrt(G_jj)) from the upper triangle of G, 1 when either norm is 0, +inf when the quotient is NaN; d* is the smallest
+    threshold at which the graph D <= t on the finite rows has a component of >= m rows, and that component is kept; S
+    is the lower median of the finite rows' norms, c_i = (alpha_i min(1, S / e_i)) / sum_kept alpha, sigma = lam S.
+    Plain Python floats (IEEE fp64, correctly rounded sqrt and division, sums in index order): given the same G the
+    kernel returns the same bits.  The threshold is found by a plain scan: the pairs in ascending order of D, a whole
+    group of equal D united at a time, the components' sizes looked at after each group.  It reads G back to the host,
+    so it serves any device and any n; the results go back to G's device.
+
+    ``margin`` (a float): 0 when more than one pair attains d*, else the smallest |D_ij - d*| over the finite rows'
+    pairs with D_ij != d* (+inf when there is none).  A perturbation of D below it changes neither the set of pairs
+    under d* nor the pair at d*, so the kept set stands."""
+    dev = G.device
+    Gl = G.detach().double().cpu().tolist()
+    n, lam = len(Gl), float(lam)
+    if n < 1 or not (0.0 <= lam < math.inf):
+        raise ValueError(f"flame_select needs n >= 1 and a finite lam >= 0 (got {n}, {lam})")
+    al = alpha.detach().double().cpu().reshape(-1).tolist()
+    fin = [i for i in range(n) if math.isfinite(Gl[i][i])]
+    nf = len(fin)
+    m = nf // 2 + 1
+    e = [math.sqrt(Gl[i][i]) if i in fin and Gl[i][i] > 0.0 else 0.0 for i in range(n)]
+    pairs = []
+    for x, i in enumerate(fin):
+        for j in fin[x + 1:]:
+            d = 1.0
+            if e[i] != 0.0 and e[j] != 0.0:
+                d = 1.0 - Gl[i][j] / (e[i] * e[j])
+                d = d if d == d else math.inf
+            pairs.append((d, i, j))
+    pairs.sort()
+    comp = {i: {i} for i in fin}  # row -> its component (shared sets)
+    kept, dstar, k = (set(fin) if nf == 1 else set()), 0.0, 0
+    while k < len(pairs) and not kept:
+        t = pairs[k][0]
+        while k < len(pairs) and pairs[k][0] == t:
+            _, i, j = pairs[k]
+            if comp[i] is not comp[j]:
+                comp[i] |= comp[j]
+                for r in comp[j]:
+                    comp[r] = comp[i]
+            k += 1
+        big = [s for s in comp.values() if len(s) >= m]
+        if big:
+            kept, dstar = big[0], t
+    at = sum(1 for d, _, _ in pairs if d == dstar) if nf > 1 else 1
+    gaps = [abs(d - dstar) for d, _, _ in pairs if d != dstar] if nf > 1 else []
+    margin = 0.0 if at > 1 else (min(gaps) if gaps else math.inf)
+    S = sorted(e[i] for i in fin)[(nf - 1) // 2] if nf else 0.0
+    den = 0.0
+    for i in range(n):
+        den += al[i] if i in kept else 0.0
+    c = [(al[i] * (1.0 if e[i] <= S else S / e[i])) / den if i in kept else 0.0 for i in range(n)]
+    t64 = lambda v: torch.tensor(v, dtype=torch.float64, device=dev)
+    return (torch.tensor([i in kept for i in range(n)], dtype=torch.bool, device=dev), t64(c),
+            t64([S, lam * S, dstar, float(m), float(nf)]), margin)
+
+
+def flame_rows(U: torch.Tensor, c: torch.Tensor, anchor: torch.Tensor, sigma, seed: int) -> torch.Tensor:
+    """anchor + sum_{j: c_j != 0} c_j (U_j - anchor) + sigma z (``k_flame_rows``): ``anchored_rows``' sum in fp64, then
+    z = ``philox_normal`` under ``flame_key(seed)`` (column p takes draw p), one rounding to U's dtype.  sigma (a number
+    or a one-element tensor) of 0: no draw, the bits of ``anchored_rows``."""
+    s = float(sigma.reshape(-1)[0]) if torch.is_tensor(sigma) else float(sigma)
+    if s == 0.0:
+        return anchored_rows(U, c, anchor)
+    g = anchor.double()
+    c = c.to(device=U.device, dtype=torch.float64)
+    acc = torch.zeros_like(g)
+    for j in range(U.shape[0]):
+        acc = acc + torch.where(c[j] != 0, c[j] * (U[j].double() - g), torch.zeros_like(g))
+    z = torch.from_numpy(philox_normal(U.shape[1], flame_key(seed))).to(U.device)
+    return ((g + acc) + s * z).to(U.dtype)
+
+
+def flame_filter(U: torch.Tensor, g: torch.Tensor, alpha: torch.Tensor, lam: float):
+    """``flame_select`` on ``gram_anchored`` -> its results without the margin."""
+    return flame_select(gram_anchored(U, g.to(U.device)), alpha, lam)[:3]

@@ -410,6 +410,49 @@ torch::Tensor anchored_rows(torch::Tensor U, torch::Tensor c, torch::Tensor anch
   return out;
 }
 
+// FLAME (agg.flame; agg.hip k_flame_select / k_flame_rows).  flame_select: G [n, n] fp64 the Gram about the centre,
+// alpha [n] fp64, lam >= 0 -> (keep [n] uint8, c [n] fp64, info [5] fp64 {S, sigma, d*, m, n'}); n outside [1, 64] is
+// refused by the launcher
+std::vector<torch::Tensor> flame_select(torch::Tensor G, torch::Tensor alpha, double lam) {
+  check_dev(G, "G", torch::kFloat64);
+  check_dev(alpha, "alpha", torch::kFloat64);
+  TORCH_CHECK(G.dim() == 2 && G.size(0) == G.size(1) && alpha.numel() == G.size(0) && alpha.device() == G.device(),
+              "flame_select: G [n, n] and alpha [n] on one device");
+  const int64_t n = G.size(0);
+  auto keep = torch::empty({n}, G.options().dtype(torch::kUInt8));  // (the kernel writes every element)
+  auto c = torch::empty({n}, G.options());
+  auto info = torch::empty({5}, G.options());
+  TORCH_CHECK(n <= (int64_t)INT_MAX &&
+                  afl_flame_select(G.data_ptr<double>(), alpha.data_ptr<double>(), (int)n, lam,
+                                   keep.data_ptr<uint8_t>(), c.data_ptr<double>(), info.data_ptr<double>(), cur()) == 0,
+              "flame_select: 1 <= n <= 64 and lam >= 0, finite (got n = ", n, ", lam = ", lam, ")");
+  AFL_CHECK_LAUNCH();
+  return {keep, c, info};
+}
+
+// flame_rows: U [N, P] fp32, c [N] fp64, anchor [P] fp32, sigma [>= 1] fp64 (device; its first element is read by the
+// kernel), key: the 64-bit Philox key -> anchor + sum_{c_j != 0} c_j (U_j - anchor) + sigma z [P]
+torch::Tensor flame_rows(torch::Tensor U, torch::Tensor c, torch::Tensor anchor, torch::Tensor sigma, int64_t key) {
+  check_dev(U, "U", torch::kFloat32);
+  check_dev(c, "c", torch::kFloat64);
+  check_dev(anchor, "anchor", torch::kFloat32);
+  TORCH_CHECK(sigma.is_cuda() && sigma.scalar_type() == torch::kFloat64 && sigma.numel() >= 1,
+              "flame_rows: sigma a device fp64 tensor");
+  TORCH_CHECK(U.dim() == 2 && U.size(0) >= 1 && U.size(0) <= INT_MAX && U.size(1) >= 1, "flame_rows: U [N, P]");
+  const int N = U.size(0);
+  const long P = U.size(1);
+  TORCH_CHECK(c.numel() == N && anchor.dim() == 1 && anchor.size(0) == P, "flame_rows: c [N], anchor [P] (got ",
+              c.numel(), " and ", anchor.numel(), " for N = ", N, ", P = ", P, ")");
+  TORCH_CHECK(c.device() == U.device() && anchor.device() == U.device() && sigma.device() == U.device(),
+              "flame_rows: every tensor on U's device");
+  auto out = torch::empty({P}, U.options());
+  TORCH_CHECK(afl_flame_rows(U.data_ptr<float>(), c.data_ptr<double>(), N, P, anchor.data_ptr<float>(),
+                             sigma.data_ptr<double>(), (uint64_t)key, out.data_ptr<float>(), cur()) == 0,
+              "flame_rows launch failed");
+  AFL_CHECK_LAUNCH();
+  return out;
+}
+
 // FoolsGold (agg.foolsgold).  hist_gram: U, H [K <= 64, P] fp32, g [P] fp32, enable [1] int32 (device), Hnew [K, P] fp32
 // (a buffer other than H) -> the Gram [K, K] fp64 of Hnew = H + (U - g) (enable 0: = H), which the pass also writes
 torch::Tensor hist_gram(torch::Tensor U, torch::Tensor g, torch::Tensor H, torch::Tensor enable, torch::Tensor Hnew) {
@@ -1169,6 +1212,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gram_anchored", &gram_anchored);
   m.def("cclip_weights", &cclip_weights);
   m.def("anchored_rows", &anchored_rows);
+  m.def("flame_select", &flame_select);
+  m.def("flame_rows", &flame_rows);
   m.def("hist_gram", &hist_gram);
   m.def("foolsgold_weights", &foolsgold_weights);
   m.def("fxsum_test", &fxsum_test);

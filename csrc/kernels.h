@@ -530,6 +530,16 @@ int afl_sign_stats(const float* U, const float* g, int K, long P, long s, long b
 int afl_signguard_select(const double* part, int nb, int n, long b, const double* alpha, double lo, double hi,
                          unsigned char* keep, unsigned char* norm_ok, int* label, double* feat, double* c, double* info,
                          double* qout, int* cout, hipStream_t s);
+// FLAME (docs/PARITY.md).  afl_flame_select (agg.hip k_flame_select): G [n][n] the Gram about the centre (n <= 64,
+// afl_gram_anchored), alpha [n], lam >= 0 -> keep [n] 0/1 (the majority cluster of the cosine distances), c [n] (the
+// weights of afl_flame_rows, clipped to the lower median norm S), info [5] = {S, sigma = lam S, d*, m, n'}.  Refused
+// instead of launched: n outside [1, 64], lam negative or not finite.  afl_flame_rows (k_flame_rows): out = g +
+// sum_{j: c_j != 0} c_j (U_j - g) + *sigma z, sigma read from the device, z the Philox4x32-10 / Box-Muller normals of
+// afl_noise_philox's scheme under ``key`` (counter = the column group of 4); *sigma == 0: afl_anchored_rows' bits.
+int afl_flame_select(const double* G, const double* alpha, int n, double lam, unsigned char* keep, double* c,
+                     double* info, hipStream_t s);
+int afl_flame_rows(const float* U, const double* c, int N, long P, const float* g, const double* sigma, uint64_t key,
+                   float* out, hipStream_t s);
 void afl_noise_philox(const float* own, float* out, long P, float sigma, uint64_t seed, hipStream_t s);
 
 // comm.hip — one-shot intra-node all-gather over IPC-mapped peer buffers (xGMI)

@@ -24,6 +24,8 @@
 //   dnc_select      DnC: top eigenpair, scores, ranked drop, mask intersection and weights, one wave
 //   sign_stats      SignGuard: squared norms about the centre and sign counts on a column window, one pass
 //   signguard_select  SignGuard: norm filter, mean-shift clustering of the sign features and clipped weights, one wave
+//   flame_select    FLAME: majority cluster of the cosine distances (spanning tree + unions), clipped weights, one wave
+//   flame_rows      FLAME: anchored_rows' sum plus sigma * N(0, 1) (Philox), sigma read from the device
 // Shared: gram_for_tiles (the host's one T = 1 .. 4 launch of gram_f64, hist_gram and dnc_gram), gram_tile_mfma and
 // gram_block_partials (the tile body of gram_f64 and hist_gram, whose Grams must agree bit for bit) and lds_load_square
 // (the matrix load of geomed_weights, cclip_weights and foolsgold_weights).  The device code of gram_f64 and dnc_gram
@@ -2157,5 +2159,216 @@ int afl_signguard_select(const double* part, int nb, int n, long b, const double
   if (n < 1 || n > GMM_MAXN || nb < 1 || b < 1 || !(lo > 0.0) || !(hi >= lo)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_signguard_select, dim3(1), dim3(64), 0, s, part, nb, n, b, alpha, lo, hi, keep, norm_ok, label,
                      feat, c, info, qout, cout);
+  return (int)hipGetLastError();
+}
+
+// ============================================================================ flame
+// FLAME (Nguyen et al., USENIX Security 2022; rule text in docs/PARITY.md) of n <= 64 rows from the Gram G of the
+// updates about the centre.  k_flame_select: one wave, lane i owns row i; contraction off, the host mirror's expression
+// shapes (``composite.flame_select``), correctly rounded sqrt and division.
+//   finite rows: G_ii finite (n' of them, m = n' / 2 + 1); e_i = sqrt(G_ii) (0 when G_ii <= 0).
+//   D_ij = 1 - G_ij / (e_i e_j) from the upper triangle of G (i < j; the lower one is its copy, so D is symmetric to
+//   the bit), 1 when e_i or e_j is 0, +inf when the quotient is NaN, D_ii = 0; D overwrites G in LDS.
+//   Prim's minimum spanning tree of the finite rows from the lowest one: n' - 1 wave-wide argmins by (key, lane); step
+//   s leaves edge s = (weight, lower row, higher row).  The edges are rank-sorted by (weight, lower, higher), then
+//   united in that order on 64-bit membership masks (lane i holds its component's) until a union holds >= m rows:
+//   its weight is d*.  Every further edge of weight d* is united too (the components of the graph D <= d* are those of
+//   any spanning tree's edges <= d*), and the component that reached m is kept.
+//   S = the lower median (rank (n' - 1) / 2 by (e, row)) of the finite rows' e; for a kept row c_i = (alpha_i scale_i) /
+//   sum_kept alpha, scale_i = e_i <= S ? 1 : S / e_i, the sum in index order; else c_i = 0.
+// out: keep [n] 0/1, c [n], info = {S, sigma = lam S, d*, m, n'}.
+__global__ void __launch_bounds__(64) k_flame_select(const double* __restrict__ G, const double* __restrict__ alpha,
+                                                     int n, double lam, unsigned char* __restrict__ keep,
+                                                     double* __restrict__ c, double* __restrict__ info) {
+#pragma clang fp contract(off)
+  __shared__ double A[GMM_MAXN * KS_LD], eb[GMM_MAXN], ew[GMM_MAXN], sw[GMM_MAXN], S_s;
+  __shared__ unsigned char ea[GMM_MAXN], eh[GMM_MAXN], sa[GMM_MAXN], sh[GMM_MAXN];
+  const int i = threadIdx.x;
+  lds_load_square(A, KS_LD, G, n);
+  __syncthreads();
+  const double gii = i < n ? A[i * KS_LD + i] : 0.0;
+  const bool fin = i < n && gram_finite(gii);
+  const unsigned long long fm = __ballot(fin);
+  const int nf = __popcll(fm), m = nf / 2 + 1;
+  const double e = fin && gii > 0.0 ? sqrt(gii) : 0.0;
+  eb[i] = e;
+  __syncthreads();
+  // ---- cosine distances: the upper triangle first (lane i reads and writes its own row only), then its copy
+  if (i < n) {
+    for (int j = i + 1; j < n; ++j) {
+      const double ej = eb[j];
+      double d = 1.0;
+      if (e != 0.0 && ej != 0.0) {
+        d = 1.0 - A[i * KS_LD + j] / (e * ej);
+        d = d == d ? d : INFINITY;
+      }
+      A[i * KS_LD + j] = d;
+    }
+    A[i * KS_LD + i] = 0.0;
+  }
+  __syncthreads();
+  if (i < n)
+    for (int j = 0; j < i; ++j) A[i * KS_LD + j] = A[j * KS_LD + i];
+  __syncthreads();
+  // ---- Prim from the lowest finite row
+  const int r0 = nf ? __ffsll((long long)fm) - 1 : 0;
+  unsigned long long tree = nf ? 1ull << r0 : 0ull;
+  double key = fin ? A[i * KS_LD + r0] : INFINITY;
+  int par = r0;
+  const int ne = nf > 0 ? nf - 1 : 0;
+  for (int s = 0; s < ne; ++s) {
+    const bool cand = fin && !((tree >> i) & 1ull);
+    double bk = cand ? key : INFINITY;
+    int bi = cand ? i : 64;
+    for (int o = 32; o; o >>= 1) {
+      const double ok = __shfl_xor(bk, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ok < bk || (ok == bk && oi < bi)) {
+        bk = ok;
+        bi = oi;
+      }
+    }
+    const int u = bi & 63;  // (the same on every lane; bi < 64: a finite row is outside the tree while s < n' - 1)
+    const int pu = __shfl(par, u, 64);
+    if (i == 0) {
+      ew[s] = bk;
+      ea[s] = (unsigned char)(u < pu ? u : pu);
+      eh[s] = (unsigned char)(u < pu ? pu : u);
+    }
+    tree |= 1ull << u;
+    const double d = A[i * KS_LD + u];
+    if (cand && i != u && d < key) {
+      key = d;
+      par = u;
+    }
+  }
+  __syncthreads();
+  // ---- the edges in the order (weight, lower row, higher row)
+  if (i < ne) {
+    const double w = ew[i];
+    const int a = ea[i], h = eh[i];
+    int rank = 0;
+    for (int t = 0; t < ne; ++t) {
+      const double wt = ew[t];
+      const int at = ea[t], ht = eh[t];
+      rank += (wt < w || (wt == w && (at < a || (at == a && ht < h)))) ? 1 : 0;
+    }
+    sw[rank] = w;
+    sa[rank] = (unsigned char)a;
+    sh[rank] = (unsigned char)h;
+  }
+  __syncthreads();
+  // ---- unions until a component holds m rows, then the ties of d*
+  unsigned long long mask = fin ? 1ull << i : 0ull;
+  bool found = false;
+  double dstar = 0.0;
+  int arow = r0;
+  for (int k = 0; k < ne; ++k) {  // (uniform)
+    const double w = sw[k];
+    if (found && w != dstar) break;
+    const int a = sa[k], h = sh[k];
+    const unsigned long long mg = __shfl(mask, a, 64) | __shfl(mask, h, 64);
+    if ((mg >> i) & 1ull) mask = mg;
+    if (!found && __popcll(mg) >= m) {
+      found = true;
+      dstar = w;
+      arow = a;
+    }
+  }
+  const unsigned long long kept = nf ? __shfl(mask, arow, 64) : 0ull;  // (n' = 1: the row's own bit)
+  const bool kp = (kept >> i) & 1ull;
+  // ---- the lower median norm, the weights
+  if (i == 0) S_s = 0.0;  // (no finite row)
+  __syncthreads();
+  int rank = 0;
+  if (fin)
+    for (int l = 0; l < n; ++l) rank += (((fm >> l) & 1ull) && (eb[l] < e || (eb[l] == e && l < i))) ? 1 : 0;
+  if (fin && rank == (nf - 1) / 2) S_s = e;
+  const double al = i < n ? alpha[i] : 0.0;
+  ew[i] = kp ? al : 0.0;  // (ew: the edges are in sw)
+  __syncthreads();
+  const double S = S_s;
+  double den = 0.0;
+  for (int j = 0; j < n; ++j) den += ew[j];
+  const double scale = e <= S ? 1.0 : S / e;
+  if (i < n) {
+    keep[i] = kp ? 1 : 0;
+    c[i] = kp ? (al * scale) / den : 0.0;
+  }
+  if (i == 0) {
+    info[0] = S;
+    info[1] = lam * S;
+    info[2] = dstar;
+    info[3] = (double)m;
+    info[4] = (double)nf;
+  }
+}
+
+int afl_flame_select(const double* G, const double* alpha, int n, double lam, unsigned char* keep, double* c,
+                     double* info, hipStream_t s) {
+  if (n < 1 || n > GMM_MAXN || !(lam >= 0.0) || !(lam < INFINITY)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_flame_select, dim3(1), dim3(64), 0, s, G, alpha, n, lam, keep, c, info);
+  return (int)hipGetLastError();
+}
+
+// k_flame_rows: out = (float)(g + sum_{j: c_j != 0} c_j (U_j - g) + sigma z), FLAME's row pass.  The sum is
+// k_anchored_rows' (rows in ascending order, differences and sum in fp64, a row with c_j == 0 not read); sigma is read
+// from the device (k_flame_select's info[1]) and z are the N(0, 1) draws of k_noise_philox's scheme under the key
+// (k0, k1): the counter is the column group p / 4, one call gives the normals of 4 consecutive columns, so a thread
+// owns one group (the last one may hold fewer than four columns).  sigma == 0: no draw, the term is left out and the
+// bits are k_anchored_rows'.
+__global__ void __launch_bounds__(256) k_flame_rows(const float* __restrict__ U, const double* __restrict__ c, int N,
+                                                    long P, const float* __restrict__ g,
+                                                    const double* __restrict__ sigma_p, uint32_t k0, uint32_t k1,
+                                                    float* __restrict__ out) {
+  const long grp = (long)blockIdx.x * blockDim.x + threadIdx.x;  // column group of 4
+  const long p0 = grp * 4;
+  if (p0 >= P) return;
+  const int nq = P - p0 < 4 ? (int)(P - p0) : 4;
+  double gp[4], acc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) gp[q] = q < nq ? (double)g[p0 + q] : 0.0;
+  for (int j = 0; j < N; ++j) {
+    const double cj = c[j];
+    if (cj != 0.0) {
+      const float* u = U + (long)j * P + p0;
+      float uv[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) uv[q] = q < nq ? u[q] : 0.0f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] += cj * ((double)uv[q] - gp[q]);
+    }
+  }
+  double r[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) r[q] = gp[q] + acc[q];
+  const double sigma = *sigma_p;
+  if (sigma != 0.0) {
+    uint32_t c0 = (uint32_t)grp, c1 = (uint32_t)(grp >> 32), c2 = 0, c3 = 0, a = k0, b = k1;
+#pragma unroll
+    for (int t = 0; t < 10; ++t) {
+      philox_round(c0, c1, c2, c3, a, b);
+      a += 0x9E3779B9u;
+      b += 0xBB67AE85u;
+    }
+    const double u0 = ((double)c0 + 1.0) * 2.3283064365386963e-10, u1 = ((double)c1 + 1.0) * 2.3283064365386963e-10;
+    const double u2 = ((double)c2 + 1.0) * 2.3283064365386963e-10, u3 = ((double)c3 + 1.0) * 2.3283064365386963e-10;
+    const double r0 = sqrt(-2.0 * log(u0)), r1 = sqrt(-2.0 * log(u2));
+    const double t0 = 6.283185307179586 * u1, t1 = 6.283185307179586 * u3;
+    r[0] += sigma * (r0 * cos(t0));
+    r[1] += sigma * (r0 * sin(t0));
+    r[2] += sigma * (r1 * cos(t1));
+    r[3] += sigma * (r1 * sin(t1));
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if (q < nq) out[p0 + q] = (float)r[q];
+}
+
+int afl_flame_rows(const float* U, const double* c, int N, long P, const float* g, const double* sigma, uint64_t key,
+                   float* out, hipStream_t s) {
+  if (N < 1 || P < 1 || sigma == nullptr) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_flame_rows, dim3(afl_cdiv(afl_cdiv(P, 4), 256)), dim3(256), 0, s, U, c, N, P, g, sigma,
+                     (uint32_t)key, (uint32_t)(key >> 32), out);
   return (int)hipGetLastError();
 }

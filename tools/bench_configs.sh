@@ -12,8 +12,8 @@ run() {
 }
 if [ "${SET:-all}" = "robust" ] || [ "${SET:-all}" = "all" ]; then
   # robust server modes (reference server.py:286-494, 682-743), each with one Min-Max attacker
-  # (multi_krum / bulyan / geomed / dnc / cclip / signguard / foolsgold: beyond the reference, docs/PARITY.md)
-  for m in trimmed_mean median krum shieldfl scionfl FLTrust gmm fltracer byzantine multi_krum bulyan geomed dnc cclip signguard; do
+  # (multi_krum / bulyan / geomed / dnc / cclip / signguard / flame / foolsgold: beyond the reference, docs/PARITY.md)
+  for m in trimmed_mean median krum shieldfl scionfl FLTrust gmm fltracer byzantine multi_krum bulyan geomed dnc cclip signguard flame; do
     run --model TransformerModel --mode $m --attackers "7:Min-Max:2"
   done
   run --model TransformerModel --mode foolsgold --attackers "7:Min-Max:2"
